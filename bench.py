@@ -12,7 +12,13 @@ collectives over xGMI, and the fused AdamW update of all 8.03e9 parameters.  Wit
 optimizer is ZeRO-1 sharded by default (gradient reduce-scatter during backward, each rank
 updates 1/N of the parameters, bf16 all-gather overlapped with the next forward); ``--zero 0``
 selects the replicated all-reduce optimizer.
-Data: synthetic random tokens; weights: random init (no network, no checkpoints).
+Data: synthetic random tokens; weights: random init (no network, no checkpoints).  Both are seeded, so two
+runs with the same arguments see identical inputs.
+
+A plain run does only what the headline figure needs: set up, warm up, time the K steps, print the line.
+``--dump-outputs DIR`` also writes what the last timed step computed (:func:`dump_outputs`).  ``--full`` adds
+everything else the benchmark reports: the all-gathered rank census, the per-rank exposed-communication spans
+with RCCL's init summary, and the daemon's dashboard poll latency.
 """
 from __future__ import annotations
 
@@ -48,6 +54,31 @@ def daemon_poll_latency() -> dict | None:
         return {"error": str(e)[:200]}
 
 
+DUMP_SAMPLE = 1 << 21  # elements kept of each flat buffer: 8 MiB as float32, 16 MiB of positions
+
+
+def dump_outputs(tr, out_dir: str) -> None:
+    """What the last timed step handed its caller, as ``<name>.npy`` in float32: the step's ``loss``, and the
+    same fixed, seeded sample of DUMP_SAMPLE positions of the flat parameter buffer after the update
+    (``params``) and of the flat gradient buffer the update consumed (``grads``); ``sample_index`` holds the
+    positions.  Rank 0 writes: the parameters are replicated; with the sharded optimizer its gradient buffer
+    is reduced only in the ranges it owns."""
+    import numpy as np
+    import torch
+
+    tr.store.wait_all_params()
+    tr.opt.wait_done()
+    n = tr.store.param_buf.numel()
+    idx = torch.arange(n) if n <= DUMP_SAMPLE else \
+        torch.randint(0, n, (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(20240)).sort().values
+    on_dev = idx.to(tr.store.param_buf.device)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "loss.npy"), np.asarray(float(tr.last_loss), dtype=np.float32).reshape(1))
+    np.save(os.path.join(out_dir, "params.npy"), tr.store.param_buf[on_dev].float().cpu().numpy())
+    np.save(os.path.join(out_dir, "grads.npy"), tr.store.grad_buf[on_dev].float().cpu().numpy())
+    np.save(os.path.join(out_dir, "sample_index.npy"), idx.double().numpy())
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -62,12 +93,18 @@ def main() -> int:
     ap.add_argument("--grad-accum", type=int, default=int(os.environ.get("TH_BENCH_ACCUM", "1")))
     ap.add_argument("--zero", type=int, default=None, help="1 = sharded optimizer (default for N > 1), 0 = replicated")
     ap.add_argument("--daemon-bench", type=int, default=1,
-                    help="rank 0 also measures the daemon's dashboard poll latency after the timed steps")
+                    help="with --full, rank 0 also measures the daemon's dashboard poll latency after the timed steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="also report the rank census, per-rank communication spans + RCCL init summary, "
+                         "and the daemon poll latency")
     args = ap.parse_args()
-    # bench-only diagnostics: RCCL's INIT log to a per-rank file summarised in the JSON line, and
-    # the exposed-communication wait spans (both off for ordinary training jobs)
-    os.environ.setdefault("TH_RCCL_INIT_LOG", "1")
+    # the exposed-communication wait spans are recorded inside the timed steps (off for ordinary training
+    # jobs); on in both modes, so a plain and a --full run time the very same step
     os.environ.setdefault("TH_COMM_TIMING", "1")
+    if args.full:  # RCCL's INIT log to a per-rank file summarised in the JSON line
+        os.environ.setdefault("TH_RCCL_INIT_LOG", "1")
 
     from tensorhive_fixed_amd.utils.blas_env import refuse_unsafe_blas_workspace
 
@@ -78,8 +115,7 @@ def main() -> int:
     from tensorhive_fixed_amd.models.llama3 import LlamaConfig
     from tensorhive_fixed_amd.ops import _lib
     from tensorhive_fixed_amd.ops.attention import attention_backend
-    from tensorhive_fixed_amd.parallel.comm_diag import comm_report
-    from tensorhive_fixed_amd.parallel.dist import barrier, init_distributed, rank_census, shutdown
+    from tensorhive_fixed_amd.parallel.dist import barrier, init_distributed, shutdown
     from tensorhive_fixed_amd.workloads.llama3_ddp import Trainer, run_timed
 
     info = init_distributed()  # binds this rank to its GPU's NUMA CPUs before HIP starts any thread
@@ -92,8 +128,8 @@ def main() -> int:
                  zero=args.zero)
     res = run_timed(tr, args.steps, args.warmup)
     emu = tr.store.comm_emu.report() if tr.store.comm_emu is not None else None  # TH_COMM_EMU rehearsal
-    census = rank_census(info)  # collective: every rank takes part, after the timed region
-    comm = comm_report(res["waits"], info)  # collective too: per-rank exposed-communication spans
+    if args.dump_outputs and info.is_main:
+        dump_outputs(tr, args.dump_outputs)
     n = info.world
     flops = cfg.flops_per_token(args.seq_len) * res["tokens_per_sec"]
     line = {
@@ -128,19 +164,26 @@ def main() -> int:
         "tflops_per_gpu": round(flops / n / 1e12, 1),
         "peak_mem_gib": round(torch.cuda.max_memory_allocated() / 2**30, 1) if torch.cuda.is_available() else None,
         "final_loss": round(res["loss"], 4),
-        # where a step's time went besides compute (max over ranks, ms per step): the compute stream's
-        # stalls on gradient buckets + parameter all-gathers, and on the overlapped optimizer
-        "exposed_comm_ms_per_step": comm["exposed_comm_ms_per_step"],
-        "allgather_wait_ms": comm["allgather_wait_ms"],
-        "opt_wait_ms": comm["opt_wait_ms"],
-        "dist": {**census, "comm": comm},
         # CUs the TN weight-gradient launches were planned for during backward (null = all 256) and the
         # one-GPU RCCL channel-footprint rehearsal, when TH_COMM_EMU asks for it (parallel/comm_emu.py)
         "tn_backward_cus": tr.bwd_cus,
         "comm_emu": emu,
     }
+    if args.full:
+        from tensorhive_fixed_amd.parallel.comm_diag import comm_report
+        from tensorhive_fixed_amd.parallel.dist import rank_census
+
+        census = rank_census(info)  # collective: every rank takes part, after the timed region
+        comm = comm_report(res["waits"], info)  # collective too: per-rank exposed-communication spans
+        # where a step's time went besides compute (max over ranks, ms per step): the compute stream's
+        # stalls on gradient buckets + parameter all-gathers, and on the overlapped optimizer
+        line["exposed_comm_ms_per_step"] = comm["exposed_comm_ms_per_step"]
+        line["allgather_wait_ms"] = comm["allgather_wait_ms"]
+        line["opt_wait_ms"] = comm["opt_wait_ms"]
+        line["dist"] = {**census, "comm": comm}
+        if info.is_main:
+            line["daemon"] = daemon_poll_latency() if args.daemon_bench else None
     if info.is_main:
-        line["daemon"] = daemon_poll_latency() if args.daemon_bench else None
         print(json.dumps(line), flush=True)
     barrier(info)  # the other ranks keep their RCCL communicator until rank 0's daemon bench is done
     shutdown()

@@ -769,8 +769,9 @@ def monitoring_overhead(window_s: float = 20.0, train_rounds: int = 2, steps: in
 
 def train_throughput(gpus: int = 1, steps: int = 10, warmup: int = 3, bucket_mb: float | None = None,
                      extra: list[str] | None = None) -> dict:
-    """Run bench.py (torchrun for gpus>1) and return its JSON line."""
-    args = ["--gpus", str(gpus), "--steps", str(steps), "--warmup", str(warmup)]
+    """Run bench.py (torchrun for gpus>1) and return its JSON line, with the rank census and the
+    communication report (``--full``)."""
+    args = ["--gpus", str(gpus), "--steps", str(steps), "--warmup", str(warmup), "--full"]
     if bucket_mb is not None:
         args += ["--bucket-mb", f"{bucket_mb:g}"]
     args += list(extra or [])

@@ -33,6 +33,29 @@ def pytest_collection_modifyitems(config, items):
             item.add_marker(skip)
 
 
+@pytest.fixture()
+def sock_dir():
+    """A short private directory for unix sockets.  ``sun_path`` holds 107 bytes, which ``tmp_path`` plus a
+    socket's name exceeds when the temp root is deep; this one leaves room for
+    ``tensorhive-events-XXXXXXXX/events.sock`` below it."""
+    import pathlib
+    import shutil
+    import tempfile
+
+    for base in (None, "/tmp", "/dev/shm", "/var/tmp"):
+        try:
+            d = tempfile.mkdtemp(prefix="th-", dir=base)
+        except OSError:
+            continue
+        if len(os.fsencode(d)) <= 60:
+            break
+        os.rmdir(d)
+    else:
+        pytest.fail("no temp directory short enough for a unix socket path")
+    yield pathlib.Path(d)
+    shutil.rmtree(d, ignore_errors=True)
+
+
 # ----------------------------------------------------------------------------- daemon fixtures
 import datetime  # noqa: E402
 import json  # noqa: E402

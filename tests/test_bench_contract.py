@@ -27,7 +27,7 @@ def test_multi_rank_bench_prints_one_json_line(tmp_path, world):
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world),
                         "--master-addr", "127.0.0.1", "--master-port", str(_port()), os.path.join(ROOT, "bench.py"),
                         "--gpus", str(world), "--steps", "2", "--warmup", "1", "--model", "tiny", "--seq-len", "64",
-                        "--micro-batch", "2", "--bucket-mb", "0.25"], capture_output=True, text=True, env=env,
+                        "--micro-batch", "2", "--bucket-mb", "0.25", "--full"], capture_output=True, text=True, env=env,
                        timeout=300, cwd=tmp_path)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -58,6 +58,38 @@ def test_multi_rank_bench_prints_one_json_line(tmp_path, world):
         assert {"allgather_ms_per_step", "opt_wait_ms_per_step", "step_ms"} <= set(row)
     assert d["exposed_comm_ms_per_step"] >= max(r["grad_sync_ms_per_step"] for r in comm["per_rank"]) - 1e-6
     assert comm["rccl"] is None  # gloo: no RCCL communicator
+
+
+def test_plain_bench_is_lean_and_dumps_reproducible_outputs(tmp_path):
+    """Without ``--full`` the line carries the headline figure but no census, communication report or daemon
+    latency; ``--dump-outputs`` writes the last step's loss and the sampled parameters / gradients as float32,
+    identical from run to run (seeded inputs), and ``--steps`` sets how many updates they have seen."""
+    import numpy as np
+
+    def run(steps, out):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps),
+                            "--warmup", "1", "--model", "tiny", "--seq-len", "64", "--micro-batch", "2",
+                            "--dump-outputs", str(out)], capture_output=True, text=True, timeout=300, cwd=tmp_path,
+                           env={**os.environ, "CUDA_VISIBLE_DEVICES": "", "HIP_VISIBLE_DEVICES": ""})
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout
+        return json.loads(lines[0]), {f[:-4]: np.load(out / f) for f in sorted(os.listdir(out))}
+
+    d, a = run(2, tmp_path / "a")
+    assert KEYS <= set(d) and d["steps"] == 2 and d["ms_per_step"] > 0 and d["dtype"] == "bf16"
+    assert abs(d["value"] - 2 * 64 / (d["ms_per_step"] / 1e3)) / d["value"] < 0.01
+    assert not {"dist", "daemon", "exposed_comm_ms_per_step"} & set(d)
+    assert set(a) == {"loss", "params", "grads", "sample_index"}
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    assert a["params"].shape == a["grads"].shape == a["sample_index"].shape and a["loss"].shape == (1,)
+    assert abs(float(a["loss"][0]) - d["final_loss"]) < 1e-3 and np.isfinite(a["params"]).all()
+    assert np.abs(a["grads"]).max() > 0
+    _, b = run(2, tmp_path / "b")
+    assert all(np.array_equal(a[k], b[k]) for k in a)
+    _, c = run(3, tmp_path / "c")  # one more timed step: another update, another batch
+    assert not np.array_equal(a["params"], c["params"]) and a["loss"][0] != c["loss"][0]
 
 
 def test_bench_refuses_a_hipblaslt_workspace_that_faults(tmp_path):

@@ -29,7 +29,7 @@ def _reports(d):
 
 
 @pytest.mark.parametrize("kind", ["asan", "tsan"])
-def test_th_run_under_sanitizers(tmp_path, kind):
+def test_th_run_under_sanitizers(tmp_path, sock_dir, kind):
     th = _build(f"th-run-{kind}")
     rep = tmp_path / "reports"
     rep.mkdir()
@@ -43,7 +43,7 @@ def test_th_run_under_sanitizers(tmp_path, kind):
     # the task-exit datagram path (--notify) runs under the sanitizer too
     import socket
 
-    ev_path = str(tmp_path / "ev.sock")
+    ev_path = str(sock_dir / "ev.sock")  # a socket path has to stay under 108 bytes
     ev = socket.socket(socket.AF_UNIX, socket.SOCK_DGRAM)
     ev.bind(ev_path)
     ev.settimeout(20)

@@ -126,10 +126,10 @@ def test_spawn_passes_the_event_socket(world, monkeypatch):
     assert d.event_socket_for("node-a") is None
 
 
-def test_agent_forwards_exit_events(tmp_path):
+def test_agent_forwards_exit_events(sock_dir):
     """Remote nodes: the node agent listens on the node's socket, samples at once and forwards the
     event on its stream, after a fresh entry."""
-    sock = str(tmp_path / "ev.sock")
+    sock = str(sock_dir / "ev.sock")
     p = subprocess.Popen([sys.executable, "-m", "tensorhive_fixed_amd.agent", "--stream", "2000", "--backend", "stub",
                           "--stub-gpus", "1", "--host", "n9", "--events", sock], stdout=subprocess.PIPE, text=True,
                          cwd=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -177,14 +177,14 @@ def test_an_event_flood_is_not_a_sampling_flood(world, monkeypatch):
     assert time.time() - t0 < 2.0
 
 
-def test_agent_coalesces_an_event_flood(tmp_path):
+def test_agent_coalesces_an_event_flood(sock_dir):
     """A burst of 300 datagrams at the node agent turns into a bounded number of samples (one per
     agent.EVENT_MIN_GAP_S at most) and at most agent.MAX_EVENTS_PER_SAMPLE events per sample."""
     import threading
 
     from tensorhive_fixed_amd import agent
 
-    sock = str(tmp_path / "ev.sock")
+    sock = str(sock_dir / "ev.sock")
     p = subprocess.Popen([sys.executable, "-m", "tensorhive_fixed_amd.agent", "--stream", "5000", "--backend", "stub",
                           "--stub-gpus", "1", "--host", "n9", "--events", sock], stdout=subprocess.PIPE, text=True,
                          cwd=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -214,17 +214,17 @@ def test_agent_coalesces_an_event_flood(tmp_path):
         p.wait(10)
 
 
-def test_agent_auto_socket_is_private_and_reported(tmp_path):
+def test_agent_auto_socket_is_private_and_reported(sock_dir):
     """``--events auto`` binds in a fresh 0711 directory (no other user can pre-create or swap the
     socket) and reports the path; the directory is gone when the agent exits."""
-    env = {**os.environ, "XDG_RUNTIME_DIR": str(tmp_path)}
+    env = {**os.environ, "XDG_RUNTIME_DIR": str(sock_dir)}
     p = subprocess.Popen([sys.executable, "-m", "tensorhive_fixed_amd.agent", "--stream", "2000", "--backend", "stub",
                           "--stub-gpus", "1", "--host", "n9", "--events", "auto"], stdout=subprocess.PIPE, text=True,
                          env=env, cwd=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     try:
         sock = json.loads(p.stdout.readline())["events_socket"]
         d = os.path.dirname(sock)
-        assert os.path.dirname(d) == str(tmp_path) and os.path.basename(d).startswith("tensorhive-events-")
+        assert os.path.dirname(d) == str(sock_dir) and os.path.basename(d).startswith("tensorhive-events-")
         assert (os.stat(d).st_mode & 0o777) == 0o711
         assert "entry" in json.loads(p.stdout.readline())
         c = socket.socket(socket.AF_UNIX, socket.SOCK_DGRAM)
@@ -237,12 +237,12 @@ def test_agent_auto_socket_is_private_and_reported(tmp_path):
     assert not os.path.exists(d)
 
 
-def test_squatted_socket_path_is_never_handed_to_tasks(tmp_path):
+def test_squatted_socket_path_is_never_handed_to_tasks(sock_dir):
     """An explicit path another process already holds: the agent warns and binds nothing, so it reports no
     socket and the daemon passes no --notify path for that node (exits are found by polling)."""
     from tensorhive_fixed_amd.core.telemetry import RemoteBackend
 
-    squat = str(tmp_path / "ev.sock")
+    squat = str(sock_dir / "ev.sock")
     with open(squat, "w") as f:
         f.write("not a socket")
     argv = [sys.executable, "-m", "tensorhive_fixed_amd.agent", "--stream", "300", "--backend", "stub", "--stub-gpus",
@@ -265,13 +265,13 @@ def test_squatted_socket_path_is_never_handed_to_tasks(tmp_path):
     finally:
         b.close()
     # and a well-behaved agent's reported path is what the backend hands out
-    argv[-1] = str(tmp_path / "ok.sock")
+    argv[-1] = str(sock_dir / "ok.sock")
     b = RemoteBackend(T(), stream_ms=300, mode="agent")
     try:
         t0 = time.time()
         while b.event_socket("n9") is None and time.time() - t0 < 20:
             b.sample("n9")
             time.sleep(0.1)
-        assert b.event_socket("n9") == str(tmp_path / "ok.sock")
+        assert b.event_socket("n9") == str(sock_dir / "ok.sock")
     finally:
         b.close()
