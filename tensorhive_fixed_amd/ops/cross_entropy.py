@@ -39,8 +39,9 @@ def ce_rows_(logits: torch.Tensor, target: torch.Tensor, grad_scale: float,
         return loss
     lf = logits.float()
     lse = torch.logsumexp(lf, dim=-1)
-    valid = target != ignore_index
-    tgt = target.clamp(min=0)
+    # as the kernel: the ignore index, a negative target and one >= V are invalid (loss 0, zero gradient row)
+    valid = (target != ignore_index) & (target >= 0) & (target < V)
+    tgt = torch.where(valid, target, torch.zeros_like(target))
     loss = torch.where(valid, lse - lf.gather(1, tgt[:, None])[:, 0], torch.zeros_like(lse))
     p = torch.softmax(lf, dim=-1)
     p[torch.arange(R), tgt] -= 1.0

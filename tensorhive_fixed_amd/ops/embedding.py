@@ -9,6 +9,13 @@ from . import _lib
 from ._grad import deliver
 
 
+def sort_tokens(ids: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    """Sorted ids and the permutation the backward kernel walks.  The kernel sums a run of equal ids in
+    permutation order, so its bit-reproducibility needs equal ids in a fixed (ascending-position) order:
+    a stable sort."""
+    return torch.sort(ids, stable=True)
+
+
 class _Embedding(torch.autograd.Function):
     @staticmethod
     def forward(ctx, tokens: torch.Tensor, w: torch.Tensor):
@@ -30,7 +37,7 @@ class _Embedding(torch.autograd.Function):
         if dy2.is_cuda:
             if dy2.dtype != torch.bfloat16 or D % 8:
                 raise ValueError("embedding backward kernel needs bf16 grads and D % 8 == 0")
-            sorted_ids, perm = torch.sort(ids)
+            sorted_ids, perm = sort_tokens(ids)
 
             def write(out: torch.Tensor, accumulate: bool) -> None:
                 if not accumulate:
