@@ -28,6 +28,7 @@ from torch import nn
 
 from ..ops.attention import qkv_attention
 from ..ops.cross_entropy import linear_cross_entropy
+from ..ops.decode_attention import KVCache, decode_attention, rope_append
 from ..ops.embedding import embedding
 from ..ops.linear import linear
 from ..ops.mlp import gate_up_swiglu
@@ -212,3 +213,119 @@ class Llama(nn.Module):
     @torch.no_grad()
     def logits(self, tokens: torch.Tensor) -> torch.Tensor:
         return torch.mm(self.hidden(tokens), self.lm_head.t()).view(*tokens.shape, -1)
+
+    # ------------------------------------------------------------------ generation (KV cache)
+    @staticmethod
+    def _need_add_norm(what: str) -> None:
+        if not ADD_NORM:
+            raise RuntimeError(f"Llama.{what} runs the fused add+norm flow only: unset TH_ADD_NORM=0 / "
+                               "TH_RMSNORM_FORK=0")
+
+    @torch.no_grad()
+    def prefill(self, tokens: torch.Tensor, prompt_lens, cache: KVCache) -> torch.Tensor:
+        """Run the left-aligned prompts ``tokens [B, S]`` through the training forward (flash attention,
+        RoPE in place on the packed qkv), copy every layer's rotated K and its V into ``cache`` and set
+        the cache lengths to ``prompt_lens``.  Returns the final-norm hidden state ``[B, dim]`` at
+        position ``prompt_lens[b] - 1``.  Padding after a prompt is masked out of every real position
+        by causality; its cache rows are dead by the lengths."""
+        self._need_add_norm("prefill")
+        c = self.cfg
+        B, S = tokens.shape
+        lens = [int(n) for n in prompt_lens]
+        if B != cache.batch or len(lens) != B or min(lens) < 1 or max(lens) > S or S > cache.max_len:
+            raise ValueError(f"prefill: prompts {lens} in a [{B}, {S}] batch do not fit the cache "
+                             f"(batch {cache.batch}, max_len {cache.max_len})")
+        Hq, Hkv, Dh = c.n_heads, c.n_kv_heads, c.head_dim
+        x = embedding(tokens, self.tok_emb).view(B * S, c.dim)
+        pending = None
+        for i, blk in enumerate(self.layers):
+            if pending is None:
+                h, x = _norm(x, blk.attn_norm, c.norm_eps)
+            else:
+                h, x = rmsnorm_add_fork(pending, x, blk.attn_norm, c.norm_eps)
+            qkv = linear(h, blk.wqkv)
+            o = qkv_attention(qkv, B, S, Hq, Hkv, Dh, c.rope_theta)  # rotates q / k of qkv in place
+            kv = qkv.view(B, S, Hq + 2 * Hkv, Dh)
+            cache.k(i)[:, :, :S].copy_(kv[:, :, Hq: Hq + Hkv].transpose(1, 2))
+            cache.v(i)[:, :, :S].copy_(kv[:, :, Hq + Hkv:].transpose(1, 2))
+            h, x = rmsnorm_add_fork(linear(o, blk.wo), x, blk.ffn_norm, c.norm_eps)
+            pending = linear(swiglu(linear(h, blk.w13)), blk.w2)
+        cache.set_lens(lens)
+        rows = torch.tensor([b * S + n - 1 for b, n in enumerate(lens)], device=tokens.device)
+        return rmsnorm_add_fork(pending[rows].contiguous(), x[rows].contiguous(), self.norm, c.norm_eps)[0]
+
+    @torch.no_grad()
+    def decode_step(self, tokens: torch.Tensor, cache: KVCache) -> torch.Tensor:
+        """One new token per sequence (``tokens [B]``) on top of ``cache`` -> f32 logits ``[B, vocab]``;
+        advances the cache lengths by one."""
+        self._need_add_norm("decode_step")
+        c = self.cfg
+        B = tokens.shape[0]
+        if tokens.dim() != 1 or B != cache.batch:
+            raise ValueError(f"decode_step: expected {cache.batch} token ids, got shape {tuple(tokens.shape)}")
+        x = embedding(tokens.view(B, 1), self.tok_emb).view(B, c.dim)
+        pending = None
+        for i, blk in enumerate(self.layers):
+            if pending is None:
+                h, x = _norm(x, blk.attn_norm, c.norm_eps)
+            else:
+                h, x = rmsnorm_add_fork(pending, x, blk.attn_norm, c.norm_eps)
+            q = rope_append(linear(h, blk.wqkv), cache, i)
+            o = decode_attention(q, cache, i, new=1)
+            h, x = rmsnorm_add_fork(linear(o, blk.wo), x, blk.ffn_norm, c.norm_eps)
+            pending = linear(swiglu(linear(h, blk.w13)), blk.w2)
+        cache.advance(1)
+        h = rmsnorm_add_fork(pending, x, self.norm, c.norm_eps)[0]
+        return torch.mm(h, self.lm_head.t()).float()
+
+    @staticmethod
+    def sample(logits: torch.Tensor, temperature: float = 0.0, top_k: int | None = None,
+               generator: torch.Generator | None = None) -> torch.Tensor:
+        """Next token ids ``[B]`` from f32 logits ``[B, vocab]``: argmax at temperature 0, else a draw
+        from softmax(logits / temperature) restricted to the ``top_k`` largest."""
+        if temperature <= 0.0:
+            return logits.argmax(-1)
+        z = logits.float() / temperature
+        if top_k is not None and 0 < top_k < z.shape[-1]:
+            kth = z.topk(top_k, dim=-1).values[:, -1:]
+            z = z.masked_fill(z < kth, float("-inf"))
+        return torch.multinomial(z.softmax(-1), 1, generator=generator)[:, 0]
+
+    @torch.no_grad()
+    def generate(self, tokens: torch.Tensor, prompt_lens=None, max_new_tokens: int = 16,
+                 temperature: float = 0.0, top_k: int | None = None,
+                 generator: torch.Generator | None = None, return_logits: bool = False,
+                 on_step=None):
+        """Continue the left-aligned prompts ``tokens [B, S]`` (``prompt_lens`` defaults to ``S`` for all)
+        by ``max_new_tokens`` tokens -> ids ``[B, max_new_tokens]`` (and the f32 logits
+        ``[B, max_new_tokens, vocab]`` of every step with ``return_logits``).  ``on_step(i)`` is called
+        after step ``i``'s token is chosen (step 0 comes from the prefill)."""
+        B, S = tokens.shape
+        lens = [S] * B if prompt_lens is None else [int(n) for n in prompt_lens]
+        if max_new_tokens < 1:
+            raise ValueError("generate: max_new_tokens must be at least 1")
+        S = max(lens) if lens else S
+        pad = -(-S // 64) * 64  # the flash forward at lengths its own tests cover
+        max_len = max(pad, S + max_new_tokens)
+        if max_len > self.cfg.max_seq_len:
+            raise ValueError(f"generate: {S} prompt + {max_new_tokens} new tokens exceed max_seq_len "
+                             f"{self.cfg.max_seq_len}")
+        cache = KVCache(self.cfg, B, max_len, tokens.device)
+        if len(lens) != B or min(lens) < 1 or S > tokens.shape[1]:
+            raise ValueError(f"generate: prompt lengths {lens} do not fit tokens of shape {tuple(tokens.shape)}")
+        padded = torch.zeros((B, pad), device=tokens.device, dtype=tokens.dtype)
+        live = torch.arange(S, device=tokens.device)[None, :] < torch.tensor(lens, device=tokens.device)[:, None]
+        padded[:, :S] = tokens[:, :S] * live  # token 0 after every prompt
+        h = self.prefill(padded, lens, cache)
+        logits = torch.mm(h, self.lm_head.t()).float()
+        out, steps = [], []
+        for i in range(max_new_tokens):
+            if i:
+                logits = self.decode_step(out[-1], cache)
+            out.append(self.sample(logits, temperature, top_k, generator))
+            if return_logits:
+                steps.append(logits)
+            if on_step is not None:
+                on_step(i)
+        ids = torch.stack(out, dim=1)
+        return (ids, torch.stack(steps, dim=1)) if return_logits else ids

@@ -50,6 +50,8 @@ _SIGS: dict[str, list] = {
     "th_gemm_tn": [P, L, P, L, P, L, I, I, I, I, I, I, P, L, I, P],
     "th_comm_emu_launch": [P, P, L, L, L, L, P, I, L, I, P, P],
     "th_comm_emu_stop": [P, I, P],
+    "th_decode_rope_append": [P, P, P, P, P, P, P, I, I, I, I, I, L, L, P],
+    "th_decode_attn": [P, P, P, P, P, P, I, I, I, I, I, L, L, I, I, I, F, P],
 }
 
 

@@ -160,7 +160,7 @@ class FlatParamStore:
         # can be exercised on a one-GPU box (tests/gpu/test_ddp_gpu.py)
         self.collectives = initialized and (self.world > 1 or forced_collectives())
         # decayed (matrices) first, then non-decayed vectors: two contiguous optimizer groups
-        ordered = [e for e in params_in_backward_order if e[2]] + [e for e in params_in_backward_order if not e[2]]
+        ordered = self._ordered(params_in_backward_order)
         offs, self.buckets = self._layout([(p, d) for _, p, d in ordered], bucket_mb)
         self.numel = self.buckets[-1].end if self.buckets else 0
         self.decay_numel = max([o + p.numel() for (_, p, d), o in zip(ordered, offs) if d], default=0)
@@ -223,6 +223,26 @@ class FlatParamStore:
         if cur is not None:
             cur.end = cur.start + _round_up(off - cur.start, quantum)
         return offs, buckets
+
+    @classmethod
+    def param_layout(cls, params_in_backward_order: list[tuple[str, torch.nn.Parameter, bool]],
+                     dtype: torch.dtype = torch.bfloat16, bucket_mb: float = 256.0, world: int = 1,
+                     sharded: bool = False) -> tuple[list[str], list[torch.nn.Parameter], list[int], int]:
+        """``(names, params, offsets, numel)`` of the flat parameter buffer a store built with these
+        arguments lays out -- the same ordering and :meth:`_layout` as ``__init__``, without
+        allocating a buffer (a checkpoint reader only needs to know where each parameter sits)."""
+        probe = object.__new__(cls)
+        probe.dtype, probe.world, probe.sharded = dtype, world, bool(sharded)
+        ordered = cls._ordered(params_in_backward_order)
+        offs, buckets = probe._layout([(p, d) for _, p, d in ordered], bucket_mb)
+        return ([n for n, _, _ in ordered], [p for _, p, _ in ordered], offs,
+                buckets[-1].end if buckets else 0)
+
+    @staticmethod
+    def _ordered(params_in_backward_order: list) -> list:
+        """Decayed (matrices) first, then non-decayed vectors: two contiguous optimizer groups."""
+        return ([e for e in params_in_backward_order if e[2]]
+                + [e for e in params_in_backward_order if not e[2]])
 
     def bucket_ranges(self) -> list[tuple[int, int]]:
         return [(b.start, b.end) for b in self.buckets]

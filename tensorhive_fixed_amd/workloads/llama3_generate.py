@@ -1,0 +1,121 @@
+"""Llama-3 bf16 generation payload: load a training checkpoint (or random-init weights) and produce
+tokens with the KV cache and the split-KV decode attention kernel (``ops/decode_attention.py``).
+
+Launched like the training payload, one process on one GPU (``python -m
+tensorhive_fixed_amd.workloads.llama3_generate``), typically as a task of the tensorhive job queue.
+It prints ``[th-gen] step=N tokens/s=X batch=B`` lines and ends with one JSON line
+``{"event": "done", "new_tokens": ..., "prefill_ms": ..., "decode_ms_per_token": ...}``.
+
+The project has no tokenizer: prompts are token ids, from ``--prompt-ids FILE`` (a JSON list of id
+lists, which may be ragged) or synthetic ones drawn like the training data.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import sys
+import time
+
+import torch
+
+from ..models.llama3 import Llama, LlamaConfig
+from ..parallel.flat import FlatParamStore
+
+
+def load_checkpoint_params(model: Llama, path: str, bucket_mb: float = 256.0) -> None:
+    """Fill ``model``'s parameters from the ``param_buf`` of a checkpoint written by ``Trainer.save``.
+
+    The flat layout is :meth:`FlatParamStore.param_layout` -- the store's own code -- so no gradient
+    or optimizer buffer is allocated.  ``bucket_mb`` only matters for a checkpoint of a sharded
+    (ZeRO-1) run, whose buckets are padded per rank: pass the training run's value."""
+    st = torch.load(path, map_location="cpu", weights_only=True)
+    zero_world = int(st.get("zero_world", torch.tensor(0)))
+    names, params, offs, numel = FlatParamStore.param_layout(
+        model.params_in_backward_order(), dtype=st["param_buf"].dtype, bucket_mb=bucket_mb,
+        world=max(1, zero_world), sharded=zero_world > 0)
+    if st["names"] != "\n".join(names):
+        raise ValueError("checkpoint does not match this model's parameter layout")
+    buf = st["param_buf"]
+    if buf.numel() != numel:
+        raise ValueError(f"checkpoint holds {buf.numel()} flat elements, this model's layout has {numel} "
+                         "(a sharded run's --bucket-mb must be given)")
+    with torch.no_grad():
+        for p, o in zip(params, offs):
+            p.copy_(buf[o: o + p.numel()].view(p.shape))
+
+
+def _prompts(args, cfg: LlamaConfig, device: torch.device) -> tuple[torch.Tensor, list[int]]:
+    if args.prompt_ids:
+        with open(args.prompt_ids) as f:
+            rows = json.load(f)
+        if not rows or not all(isinstance(r, list) and r for r in rows):
+            raise ValueError("--prompt-ids: expected a JSON list of non-empty id lists")
+        if any(not 0 <= int(t) < cfg.vocab_size for r in rows for t in r):
+            raise ValueError(f"--prompt-ids: ids must be in [0, {cfg.vocab_size})")
+        lens = [len(r) for r in rows]
+        tokens = torch.zeros((len(rows), max(lens)), dtype=torch.long)
+        for b, r in enumerate(rows):
+            tokens[b, : len(r)] = torch.tensor(r, dtype=torch.long)
+        return tokens.to(device), lens
+    gen = torch.Generator(device=device)
+    gen.manual_seed(args.seed)
+    tokens = torch.randint(0, cfg.vocab_size, (args.batch, args.prompt_len), device=device, generator=gen)
+    return tokens, [args.prompt_len] * args.batch
+
+
+def main(argv: list[str] | None = None) -> int:
+    ap = argparse.ArgumentParser(description="Llama-3 bf16 generation on MI355X (KV cache, split-KV decode)")
+    ap.add_argument("--model", default="llama3-8b")
+    ap.add_argument("--ckpt", default=None, help="checkpoint written by the training payload (default: random init)")
+    ap.add_argument("--batch", type=int, default=8)
+    ap.add_argument("--prompt-len", type=int, default=512)
+    ap.add_argument("--prompt-ids", default=None, help="JSON file: a list of token-id lists (may be ragged)")
+    ap.add_argument("--max-new-tokens", type=int, default=64)
+    ap.add_argument("--temperature", type=float, default=0.0)
+    ap.add_argument("--top-k", type=int, default=None)
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--log-every", type=int, default=8)
+    ap.add_argument("--device", default=None, help="default: cuda when available, else cpu")
+    args = ap.parse_args(argv)
+    from ..utils.blas_env import refuse_unsafe_blas_workspace
+
+    refuse_unsafe_blas_workspace("th-gen")
+    device = torch.device(args.device or ("cuda" if torch.cuda.is_available() else "cpu"))
+    cfg = LlamaConfig.named(args.model)
+    model = Llama(cfg, device=device, dtype=torch.bfloat16, seed=args.seed)
+    if args.ckpt:
+        load_checkpoint_params(model, args.ckpt)
+    tokens, lens = _prompts(args, cfg, device)
+    batch = tokens.shape[0]
+    sampler = torch.Generator(device=device)
+    sampler.manual_seed(args.seed + 1)
+
+    def sync() -> float:
+        if device.type == "cuda":
+            torch.cuda.synchronize(device)
+        return time.perf_counter()
+
+    marks = {"t0": sync(), "last": None, "last_step": 0}
+
+    def on_step(i: int) -> None:
+        if i == 0:
+            marks["prefill"] = marks["last"] = sync()
+        elif i % args.log_every == 0 or i == args.max_new_tokens - 1:
+            now = sync()
+            tps = batch * (i - marks["last_step"]) / max(now - marks["last"], 1e-9)
+            print(f"[th-gen] step={i} tokens/s={tps:.1f} batch={batch}", flush=True)
+            marks["last"], marks["last_step"] = now, i
+
+    ids = model.generate(tokens, lens, max_new_tokens=args.max_new_tokens, temperature=args.temperature,
+                         top_k=args.top_k, generator=sampler, on_step=on_step)
+    end = sync()
+    decode_steps = args.max_new_tokens - 1
+    print(json.dumps({"event": "done", "new_tokens": int(ids.numel()),
+                      "prefill_ms": round(1000.0 * (marks["prefill"] - marks["t0"]), 3),
+                      "decode_ms_per_token": round(1000.0 * (end - marks["prefill"]) / decode_steps, 3)
+                      if decode_steps else None}), flush=True)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
