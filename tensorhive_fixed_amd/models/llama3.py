@@ -29,6 +29,8 @@ from torch import nn
 from ..ops.attention import qkv_attention
 from ..ops.cross_entropy import linear_cross_entropy
 from ..ops.decode_attention import KVCache, decode_attention, rope_append
+from ..ops.decode_linear import decode_gate_up_swiglu, decode_linear
+from ..ops.decode_linear import preferred as dl_preferred
 from ..ops.embedding import embedding
 from ..ops.linear import linear
 from ..ops.mlp import gate_up_swiglu
@@ -255,14 +257,17 @@ class Llama(nn.Module):
         return rmsnorm_add_fork(pending[rows].contiguous(), x[rows].contiguous(), self.norm, c.norm_eps)[0]
 
     @torch.no_grad()
-    def decode_step(self, tokens: torch.Tensor, cache: KVCache) -> torch.Tensor:
+    def decode_step(self, tokens: torch.Tensor, cache: KVCache, stream_gemm: bool = False) -> torch.Tensor:
         """One new token per sequence (``tokens [B]``) on top of ``cache`` -> f32 logits ``[B, vocab]``;
-        advances the cache lengths by one."""
+        advances the cache lengths by one.  ``stream_gemm`` runs the projections and the LM head on the
+        weight-streaming kernel of ``ops/decode_linear.py`` wherever its ``preferred`` allows."""
         self._need_add_norm("decode_step")
         c = self.cfg
         B = tokens.shape[0]
         if tokens.dim() != 1 or B != cache.batch:
             raise ValueError(f"decode_step: expected {cache.batch} token ids, got shape {tuple(tokens.shape)}")
+        if stream_gemm:
+            return self._decode_step_stream(tokens, cache)
         x = embedding(tokens.view(B, 1), self.tok_emb).view(B, c.dim)
         pending = None
         for i, blk in enumerate(self.layers):
@@ -276,6 +281,37 @@ class Llama(nn.Module):
             pending = linear(swiglu(linear(h, blk.w13)), blk.w2)
         cache.advance(1)
         h = rmsnorm_add_fork(pending, x, self.norm, c.norm_eps)[0]
+        return torch.mm(h, self.lm_head.t()).float()
+
+    def _decode_step_stream(self, tokens: torch.Tensor, cache: KVCache) -> torch.Tensor:
+        """``decode_step`` with every GEMM on ``decode_linear`` where ``preferred`` allows (gate|up and
+        SwiGLU in one call, f32 logits from the f32 accumulator); any other shape, such as a batch
+        above 16 or one measured faster on hipBLASLt, takes the GEMM of the default path."""
+        c = self.cfg
+        B = tokens.shape[0]
+
+        def proj(a, w):
+            return decode_linear(a, w) if dl_preferred(B, w.shape[0], w.shape[1]) else linear(a, w)
+
+        x = embedding(tokens.view(B, 1), self.tok_emb).view(B, c.dim)
+        pending = None
+        for i, blk in enumerate(self.layers):
+            if pending is None:
+                h, x = _norm(x, blk.attn_norm, c.norm_eps)
+            else:
+                h, x = rmsnorm_add_fork(pending, x, blk.attn_norm, c.norm_eps)
+            q = rope_append(proj(h, blk.wqkv), cache, i)
+            o = decode_attention(q, cache, i, new=1)
+            h, x = rmsnorm_add_fork(proj(o, blk.wo), x, blk.ffn_norm, c.norm_eps)
+            if dl_preferred(B, c.ffn_dim, c.dim):
+                a = decode_gate_up_swiglu(h, blk.w13)
+            else:
+                a = swiglu(linear(h, blk.w13))
+            pending = proj(a, blk.w2)
+        cache.advance(1)
+        h = rmsnorm_add_fork(pending, x, self.norm, c.norm_eps)[0]
+        if dl_preferred(B, c.vocab_size, c.dim):
+            return decode_linear(h, self.lm_head, out_dtype=torch.float32)
         return torch.mm(h, self.lm_head.t()).float()
 
     @staticmethod
@@ -295,11 +331,12 @@ class Llama(nn.Module):
     def generate(self, tokens: torch.Tensor, prompt_lens=None, max_new_tokens: int = 16,
                  temperature: float = 0.0, top_k: int | None = None,
                  generator: torch.Generator | None = None, return_logits: bool = False,
-                 on_step=None):
+                 on_step=None, stream_gemm: bool = False):
         """Continue the left-aligned prompts ``tokens [B, S]`` (``prompt_lens`` defaults to ``S`` for all)
         by ``max_new_tokens`` tokens -> ids ``[B, max_new_tokens]`` (and the f32 logits
         ``[B, max_new_tokens, vocab]`` of every step with ``return_logits``).  ``on_step(i)`` is called
-        after step ``i``'s token is chosen (step 0 comes from the prefill)."""
+        after step ``i``'s token is chosen (step 0 comes from the prefill).  ``stream_gemm`` is passed to
+        every ``decode_step``; the prefill is the same either way."""
         B, S = tokens.shape
         lens = [S] * B if prompt_lens is None else [int(n) for n in prompt_lens]
         if max_new_tokens < 1:
@@ -321,7 +358,7 @@ class Llama(nn.Module):
         out, steps = [], []
         for i in range(max_new_tokens):
             if i:
-                logits = self.decode_step(out[-1], cache)
+                logits = self.decode_step(out[-1], cache, stream_gemm=stream_gemm)
             out.append(self.sample(logits, temperature, top_k, generator))
             if return_logits:
                 steps.append(logits)

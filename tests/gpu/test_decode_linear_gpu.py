@@ -1,0 +1,201 @@
+"""The gfx950 weight-streaming linear (csrc/decode_linear.hip) on the GPU: all three epilogues against
+the fp64 oracles of ``tests/decode_linear_oracles.py`` in every template instance, memory discipline
+around x / W / y, row independence, bit reproducibility, the C entry point's rejections, and
+``stream_gemm`` through ``decode_step`` and ``generate``.  ``pytest -s`` prints the worst
+``err / bound`` per form when the module finishes."""
+import functools
+
+import pytest
+import torch
+
+from tests import decode_linear_oracles as dlo
+from tests import kernel_oracles as ko
+from tests.kernel_oracles import assert_rounded_close
+
+pytestmark = pytest.mark.gpu
+
+DEV = "cuda"
+BF = torch.bfloat16
+ULP = 2.0 ** -8
+PAD = 4096  # elements around every slice of the memory-discipline test
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _lib_loaded():
+    from tensorhive_fixed_amd.ops import _lib
+    _lib.load(build_if_missing=True)
+    assert hasattr(_lib.load(), "th_decode_linear")
+    yield
+    print("\nworst err/bound per form")
+    for k, v in sorted(ko.WORST.items()):
+        if k.startswith("gpu decode_"):
+            print(f"  {k[4:]:<28s} {v:.3f}")
+
+
+@functools.lru_cache(maxsize=None)
+def _case(M, N, K):
+    """Inputs and both fp64 references, computed once per shape and shared by every test."""
+    x, w = dlo.inputs(M, N, K, DEV)
+    return x, w, dlo.linear_oracle(x, w), dlo.swiglu_oracle(x, w)
+
+
+def _check_forms(M, N, K, run_linear, run_swiglu):
+    """Each form under its bound.  fp32_term: the default coefficient of ``mag`` stands while the
+    kernel's longest chain of dependent f32 additions is within it, else chain length x 2^-24 with
+    the chain of ``decode_linear_oracles.chain_length`` (32 additions per MFMA and k-step on each of
+    two accumulators, their sum, and the merge of the 4 waves)."""
+    _, _, (ref, mag), (sref, smag) = _case(M, N, K)
+    assert_rounded_close(run_linear(BF), ref, mag, "gpu decode_linear bf16", fp32_term=dlo.fp32_term(K, BF))
+    assert_rounded_close(run_linear(torch.float32), ref, mag, "gpu decode_linear f32",
+                         fp32_term=dlo.fp32_term(K, torch.float32))
+    assert_rounded_close(run_swiglu(), sref, smag, "gpu decode_gate_up_swiglu", fp32_term=dlo.fp32_term(K, BF))
+
+
+def _tid(t):
+    return f"tiles{t}"
+
+
+@pytest.mark.parametrize("tiles", dlo.TILES, ids=_tid)
+@pytest.mark.parametrize("M,N,K", dlo.SHAPES, ids=lambda v: str(v))
+def test_forms_against_fp64(M, N, K, tiles):
+    from tensorhive_fixed_amd.ops.decode_linear import decode_gate_up_swiglu, decode_linear
+
+    x, w, _, _ = _case(M, N, K)
+    _check_forms(M, N, K, lambda dt: decode_linear(x, w, out_dtype=dt, tiles=tiles),
+                 lambda: decode_gate_up_swiglu(x, w, tiles=tiles))
+
+
+def _framed(t, fill):
+    """A copy of ``t`` in the middle of a larger buffer filled with ``fill``; returns (buffer, view)."""
+    buf = torch.full((t.numel() + 2 * PAD,), fill, device=DEV, dtype=t.dtype)
+    view = buf[PAD: PAD + t.numel()].view(t.shape)
+    view.copy_(t)
+    return buf, view
+
+
+def _raw(x, w, y, N, mode, tiles):
+    from tensorhive_fixed_amd.ops import _lib
+    _lib.call("th_decode_linear", x.data_ptr(), w.data_ptr(), y.data_ptr(), x.shape[0], N, x.shape[1], mode, tiles,
+              _lib.stream_ptr(torch.device(DEV)))
+    torch.cuda.synchronize()
+
+
+@pytest.mark.parametrize("tiles", [1, 2], ids=_tid)
+@pytest.mark.parametrize("M,N,K", dlo.SHAPES, ids=lambda v: str(v))
+def test_memory_discipline(M, N, K, tiles):
+    """x, W and y are slices in the middle of larger buffers: NaN around x and W, a bit pattern around
+    y.  A padded row of M, or a weight row past a partial or dead tile, that is read into a live
+    output shows as NaN; one that is written breaks the pattern."""
+    x, w, _, _ = _case(M, N, K)
+    _, xs = _framed(x, float("nan"))
+    _, ws = _framed(w, float("nan"))
+    outs = {}
+    for mode, dt, cols in ((0, BF, N), (1, torch.float32, N), (2, BF, N // 2)):
+        sentinel = 0x5A5A if dt == BF else 0x5A5A5A5A
+        ibuf = torch.full((M * cols + 2 * PAD,), sentinel, device=DEV, dtype=torch.int16 if dt == BF else torch.int32)
+        y = ibuf.view(dt)[PAD: PAD + M * cols].view(M, cols)
+        _raw(xs, ws, y, N, mode, tiles)
+        assert bool(torch.isfinite(y.float()).all()), f"mode {mode}: non-finite output"
+        assert bool((ibuf[:PAD] == sentinel).all()) and bool((ibuf[PAD + M * cols:] == sentinel).all()), \
+            f"mode {mode}: written outside y"
+        outs[mode] = y.clone()
+    _check_forms(M, N, K, lambda dt: outs[0] if dt == BF else outs[1], lambda: outs[2])
+
+
+@pytest.mark.parametrize("tiles", dlo.TILES, ids=_tid)
+def test_row_independence(tiles):
+    from tensorhive_fixed_amd.ops.decode_linear import decode_gate_up_swiglu, decode_linear
+
+    x, w, _, _ = _case(8, 272, 512)
+    x2 = x.clone()
+    x2[1:] = dlo.inputs(8, 272, 512, DEV, seed=1)[0][1:] * 3
+    assert torch.equal(x2[0], x[0]) and not torch.equal(x2[1:], x[1:])
+    for dt in (BF, torch.float32):
+        a, b = decode_linear(x, w, out_dtype=dt, tiles=tiles), decode_linear(x2, w, out_dtype=dt, tiles=tiles)
+        assert torch.equal(a[0], b[0]) and not torch.equal(a[1:], b[1:])
+    a, b = decode_gate_up_swiglu(x, w, tiles=tiles), decode_gate_up_swiglu(x2, w, tiles=tiles)
+    assert torch.equal(a[0], b[0]) and not torch.equal(a[1:], b[1:])
+
+
+@pytest.mark.parametrize("tiles", dlo.TILES, ids=_tid)
+@pytest.mark.parametrize("M,N,K", [(8, 272, 512), (16, 32, 14336)], ids=lambda v: str(v))
+def test_bit_reproducible(M, N, K, tiles):
+    from tensorhive_fixed_amd.ops.decode_linear import decode_gate_up_swiglu, decode_linear
+
+    x, w, _, _ = _case(M, N, K)
+    for dt in (BF, torch.float32):
+        assert torch.equal(decode_linear(x, w, out_dtype=dt, tiles=tiles), decode_linear(x, w, out_dtype=dt, tiles=tiles))
+    assert torch.equal(decode_gate_up_swiglu(x, w, tiles=tiles), decode_gate_up_swiglu(x, w, tiles=tiles))
+
+
+def test_entry_point_rejections():
+    """Straight through the C ABI: a negative code, no launch, the output untouched."""
+    from tensorhive_fixed_amd.ops import _lib
+
+    fn = _lib.load().th_decode_linear
+    stream = _lib.stream_ptr(torch.device(DEV))
+    x = torch.ones(17, 512, device=DEV, dtype=BF)
+    w = torch.ones(32, 512, device=DEV, dtype=BF)
+    y = torch.full((17, 32), 7.0, device=DEV, dtype=torch.float32)
+    # (M, N, K, mode, tiles): M = 17 and 0, K and N off the rule, an odd half of w13, no such mode / tile count
+    bad = [(17, 32, 512, 0, 1), (0, 32, 512, 0, 1), (8, 32, 320, 0, 1), (8, 32, 128, 1, 2), (8, 24, 512, 0, 1),
+           (8, 40, 512, 2, 2), (8, 32, 512, 3, 1), (8, 32, 512, 0, 3), (8, 32, 512, 2, 0)]
+    for M, N, K, mode, tiles in bad:
+        rc = fn(x.data_ptr(), w.data_ptr(), y.data_ptr(), M, N, K, mode, tiles, stream)
+        assert rc < 0, (M, N, K, mode, tiles, rc)
+    torch.cuda.synchronize()
+    assert bool((y == 7.0).all())
+    assert fn(x.data_ptr(), w.data_ptr(), y.data_ptr(), 8, 32, 512, 1, 2, stream) == 0  # and a good one runs
+    torch.cuda.synchronize()
+    assert bool((y[:8] == 512.0).all()) and bool((y[8:] == 7.0).all())
+
+
+@functools.lru_cache(maxsize=None)
+def _tiny_pair():
+    from tensorhive_fixed_amd.models.llama3 import Llama, LlamaConfig
+
+    cfg = LlamaConfig.tiny()
+    cpu = Llama(cfg, device="cpu", seed=3)
+    gpu = Llama(cfg, device=DEV, seed=0)
+    gpu.load_state_dict(cpu.state_dict())
+    tokens = torch.randint(0, cfg.vocab_size, (2, 64), generator=torch.Generator().manual_seed(11))
+    return cpu, gpu, tokens
+
+
+def _teacher_forced(model, tokens, lens, steps):
+    """Incremental logits [B, 1 + steps, vocab] with ``stream_gemm`` (prefill padded to 64 as ``generate`` does)."""
+    from tensorhive_fixed_amd.ops.decode_attention import KVCache
+
+    cache = KVCache(model.cfg, tokens.shape[0], 64, tokens.device)
+    prompt = torch.zeros_like(tokens)
+    for b, n in enumerate(lens):
+        prompt[b, :n] = tokens[b, :n]
+    h = model.prefill(prompt, lens, cache)
+    out = [torch.mm(h, model.lm_head.t()).float()]
+    for i in range(steps):
+        nxt = torch.stack([tokens[b, n + i] for b, n in enumerate(lens)])
+        out.append(model.decode_step(nxt, cache, stream_gemm=True))
+    return torch.stack(out, dim=1)
+
+
+def test_stream_gemm_logits_no_worse_than_the_full_forward():
+    cpu, gpu, tokens = _tiny_pair()
+    lens, steps = [5, 17], 20
+    ref = cpu.logits(tokens).float()  # CPU fp32-path logits of the same weights
+    full = gpu.logits(tokens.to(DEV)).float().cpu()
+    inc = _teacher_forced(gpu, tokens.to(DEV), lens, steps).cpu()
+    rows = [slice(n - 1, n + steps) for n in lens]
+    e_new = max((inc[b] - ref[b, r]).abs().max().item() for b, r in enumerate(rows))
+    e_full = max((full[b, r] - ref[b, r]).abs().max().item() for b, r in enumerate(rows))
+    peak = max(ref[b, r].abs().max().item() for b, r in enumerate(rows))
+    print(f"e_new {e_new:.5f}  e_full {e_full:.5f}  max|logit| {peak:.4f}")
+    assert e_new <= 2 * e_full + ULP * peak
+
+
+def test_generate_stream_gemm_on_gpu():
+    _, gpu, tokens = _tiny_pair()
+    ids, logits = gpu.generate(tokens[:, :17].to(DEV), [5, 17], max_new_tokens=8, return_logits=True,
+                               stream_gemm=True)
+    assert ids.shape == (2, 8) and logits.shape == (2, 8, gpu.cfg.vocab_size) and logits.dtype == torch.float32
+    assert int(ids.min()) >= 0 and int(ids.max()) < gpu.cfg.vocab_size
+    assert torch.equal(ids, logits.argmax(-1))
