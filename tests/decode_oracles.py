@@ -30,6 +30,46 @@ def nan_dead_cache(Hq: int, Hkv: int, lens: list[int], device, seed: int = 0):
     return cache, q
 
 
+PROFILE_LENS = [1024, 700, 257]
+HEAD_GAINS = (1.0, 0.8, 0.6, 0.4)  # a of q head h is HEAD_GAINS[h % 4]: one workgroup's heads disagree on the max
+
+
+def profile_dead_cache(Hq: int, Hkv: int, lens: list[int], profile: str, device, seed: int = 0):
+    """``nan_dead_cache`` with a score profile of ``tests/attention_oracles.py`` along the key axis of
+    every sequence (over its own length) and a per-head gain on q: the log2-domain score of (head h,
+    key j) is the randn score plus ``HEAD_GAINS[h % 4] * b_j``."""
+    from tests import attention_oracles as ao
+
+    g = torch.Generator().manual_seed(seed)
+    cache = KVCache(attn_cfg(Hq, Hkv), len(lens), SMAX, device)
+    kv = torch.randn(cache.kv.shape, generator=g, dtype=torch.float64)
+    e = ao.bias_direction()
+    for b, n in enumerate(lens):
+        kv[0, 0, b, :, :n] += ao.key_bias(profile, n)[:, None] * e / (16 * ao.C_LOG2)
+        kv[:, :, b, :, n:] = float("nan")
+    cache.kv.copy_(kv.to(torch.bfloat16))
+    cache.set_lens(lens)
+    q = torch.randn(len(lens), Hq, 128, generator=g, dtype=torch.float64)
+    q += torch.tensor([HEAD_GAINS[h % 4] for h in range(Hq)], dtype=torch.float64)[None, :, None] * e
+    return cache, q.reshape(len(lens), Hq * 128).to(torch.bfloat16).to(device)
+
+
+def assert_rows_close(o: torch.Tensor, ref: torch.Tensor, Hq: int) -> tuple[float, float]:
+    """The bounds of ``assert_attention_close`` on every (sequence, q head) row by itself; returns
+    the worst row's max-abs and relative error."""
+    o = o.detach().cpu().double().view(ref.shape[0], Hq, 128)
+    ref = ref.view(ref.shape[0], Hq, 128)
+    assert torch.isfinite(o).all(), "non-finite output"
+    err = (o - ref).abs().amax(-1)
+    rel = (o - ref).norm(dim=-1) / ref.norm(dim=-1)
+    print(f"worst row: max abs err {err.max().item():.3e}  rel err {rel.max().item():.3e}")
+    b, h = divmod(int(err.argmax()), Hq)
+    assert err.max().item() < 2e-2, f"sequence {b} head {h}: max abs err {err.max().item()}"
+    b, h = divmod(int(rel.argmax()), Hq)
+    assert rel.max().item() < 1e-2, f"sequence {b} head {h}: relative err {rel.max().item()}"
+    return err.max().item(), rel.max().item()
+
+
 def attention_fp64(q: torch.Tensor, cache: KVCache, layer: int = 0) -> torch.Tensor:
     """fp64 softmax attention of the bf16 inputs over the live rows -> [B, Hq*128] float64 (CPU)."""
     B, Hq, Hkv = cache.batch, cache.n_heads, cache.n_kv_heads
