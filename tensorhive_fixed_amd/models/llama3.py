@@ -268,6 +268,15 @@ class Llama(nn.Module):
             raise ValueError(f"decode_step: expected {cache.batch} token ids, got shape {tuple(tokens.shape)}")
         if stream_gemm:
             return self._decode_step_stream(tokens, cache)
+        return self._decode_step_plain(tokens, cache)
+
+    def _decode_step_plain(self, tokens: torch.Tensor, cache: KVCache, device_geometry: bool = False,
+                           advance=None) -> torch.Tensor:
+        """The body of ``decode_step`` on hipBLASLt GEMMs.  ``advance`` replaces ``cache.advance(1)``
+        and ``device_geometry`` is passed to ``decode_attention``: both are what a captured step
+        (``decode_graph``) changes, which must not read the host lengths or move them."""
+        c = self.cfg
+        B = tokens.shape[0]
         x = embedding(tokens.view(B, 1), self.tok_emb).view(B, c.dim)
         pending = None
         for i, blk in enumerate(self.layers):
@@ -276,17 +285,22 @@ class Llama(nn.Module):
             else:
                 h, x = rmsnorm_add_fork(pending, x, blk.attn_norm, c.norm_eps)
             q = rope_append(linear(h, blk.wqkv), cache, i)
-            o = decode_attention(q, cache, i, new=1)
+            o = decode_attention(q, cache, i, new=1, device_geometry=device_geometry)
             h, x = rmsnorm_add_fork(linear(o, blk.wo), x, blk.ffn_norm, c.norm_eps)
             pending = linear(swiglu(linear(h, blk.w13)), blk.w2)
-        cache.advance(1)
+        if advance is None:
+            cache.advance(1)
+        else:
+            advance()
         h = rmsnorm_add_fork(pending, x, self.norm, c.norm_eps)[0]
         return torch.mm(h, self.lm_head.t()).float()
 
-    def _decode_step_stream(self, tokens: torch.Tensor, cache: KVCache) -> torch.Tensor:
+    def _decode_step_stream(self, tokens: torch.Tensor, cache: KVCache, device_geometry: bool = False,
+                            advance=None) -> torch.Tensor:
         """``decode_step`` with every GEMM on ``decode_linear`` where ``preferred`` allows (gate|up and
         SwiGLU in one call, f32 logits from the f32 accumulator); any other shape, such as a batch
-        above 16 or one measured faster on hipBLASLt, takes the GEMM of the default path."""
+        above 16 or one measured faster on hipBLASLt, takes the GEMM of the default path.
+        ``device_geometry`` and ``advance`` as in ``_decode_step_plain``."""
         c = self.cfg
         B = tokens.shape[0]
 
@@ -301,18 +315,29 @@ class Llama(nn.Module):
             else:
                 h, x = rmsnorm_add_fork(pending, x, blk.attn_norm, c.norm_eps)
             q = rope_append(proj(h, blk.wqkv), cache, i)
-            o = decode_attention(q, cache, i, new=1)
+            o = decode_attention(q, cache, i, new=1, device_geometry=device_geometry)
             h, x = rmsnorm_add_fork(proj(o, blk.wo), x, blk.ffn_norm, c.norm_eps)
             if dl_preferred(B, c.ffn_dim, c.dim):
                 a = decode_gate_up_swiglu(h, blk.w13)
             else:
                 a = swiglu(linear(h, blk.w13))
             pending = proj(a, blk.w2)
-        cache.advance(1)
+        if advance is None:
+            cache.advance(1)
+        else:
+            advance()
         h = rmsnorm_add_fork(pending, x, self.norm, c.norm_eps)[0]
         if dl_preferred(B, c.vocab_size, c.dim):
             return decode_linear(h, self.lm_head, out_dtype=torch.float32)
         return torch.mm(h, self.lm_head.t()).float()
+
+    @torch.no_grad()
+    def decode_graph(self, cache: KVCache, stream_gemm: bool = False):
+        """``decode_step`` on ``cache`` captured into a graph (``models/decode_graph.py``): the returned
+        object's ``step(tokens)`` replays it with one launch per token.  On the CPU it runs the eager step."""
+        from .decode_graph import DecodeGraph
+
+        return DecodeGraph(self, cache, stream_gemm=stream_gemm)
 
     @staticmethod
     def sample(logits: torch.Tensor, temperature: float = 0.0, top_k: int | None = None,
@@ -331,12 +356,13 @@ class Llama(nn.Module):
     def generate(self, tokens: torch.Tensor, prompt_lens=None, max_new_tokens: int = 16,
                  temperature: float = 0.0, top_k: int | None = None,
                  generator: torch.Generator | None = None, return_logits: bool = False,
-                 on_step=None, stream_gemm: bool = False):
+                 on_step=None, stream_gemm: bool = False, graph: bool = False):
         """Continue the left-aligned prompts ``tokens [B, S]`` (``prompt_lens`` defaults to ``S`` for all)
         by ``max_new_tokens`` tokens -> ids ``[B, max_new_tokens]`` (and the f32 logits
         ``[B, max_new_tokens, vocab]`` of every step with ``return_logits``).  ``on_step(i)`` is called
         after step ``i``'s token is chosen (step 0 comes from the prefill).  ``stream_gemm`` is passed to
-        every ``decode_step``; the prefill is the same either way."""
+        every ``decode_step``; the prefill is the same either way.  ``graph`` captures the decode step
+        once after the prefill (``decode_graph``) and replays it for every further token."""
         B, S = tokens.shape
         lens = [S] * B if prompt_lens is None else [int(n) for n in prompt_lens]
         if max_new_tokens < 1:
@@ -355,13 +381,16 @@ class Llama(nn.Module):
         padded[:, :S] = tokens[:, :S] * live  # token 0 after every prompt
         h = self.prefill(padded, lens, cache)
         logits = torch.mm(h, self.lm_head.t()).float()
+        captured = self.decode_graph(cache, stream_gemm=stream_gemm) if graph and max_new_tokens > 1 else None
         out, steps = [], []
         for i in range(max_new_tokens):
-            if i:
+            if i and captured is not None:
+                logits = captured.step(out[-1])
+            elif i:
                 logits = self.decode_step(out[-1], cache, stream_gemm=stream_gemm)
             out.append(self.sample(logits, temperature, top_k, generator))
             if return_logits:
-                steps.append(logits)
+                steps.append(logits.clone() if captured is not None else logits)  # a replay reuses its output
             if on_step is not None:
                 on_step(i)
         ids = torch.stack(out, dim=1)

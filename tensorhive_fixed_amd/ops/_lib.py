@@ -52,6 +52,7 @@ _SIGS: dict[str, list] = {
     "th_comm_emu_stop": [P, I, P],
     "th_decode_rope_append": [P, P, P, P, P, P, P, I, I, I, I, I, L, L, P],
     "th_decode_attn": [P, P, P, P, P, P, I, I, I, I, I, L, L, I, I, I, F, P],
+    "th_decode_attn_dev": [P, P, P, P, P, P, I, I, I, I, I, L, L, I, I, I, I, F, P],
     "th_decode_linear": [P, P, P, I, L, I, I, I, P],
 }
 

@@ -20,6 +20,19 @@
 //                        (m, l, acc[rep][128]) f32 to the caller's workspace.
 //                        th_decode_attn then runs the combine kernel: the nsplit partials of every
 //                        (b, q_head) merged in split order, no atomics -> bit-reproducible bf16 o.
+// th_decode_attn_dev     the same kernel body under a grid fixed by the caller, (nsplit_cap, Hkv, B), for
+//                        a launch captured into a graph: the split geometry is derived on the device
+//                        from kv_len, which grows between replays.  Every workgroup reduces the B
+//                        lengths itself (each wave: a strided loop over kv_len and a cross-lane max in DPP steps, so
+//                        no LDS, no barrier and no second kernel; B <= 65535, in practice <= 64, and the
+//                        lengths are L2 hits) and applies the host rule of ops/decode_attention.py:
+//                          longest = max_b clamp(kv_len[b] + extra, 0, Smax)
+//                          ns_eff  = max(1, min(want, longest / min_keys, nsplit_cap))
+//                          chunk   = max(1, ceil(longest / ns_eff))
+//                        Splits >= ns_eff read nothing and write the neutral element, which the
+//                        combine kernel (run over nsplit_cap partials) skips, so the live partials and
+//                        their merge order are those of th_decode_attn with (ns_eff, chunk): the same
+//                        bits.
 #include "th_common.h"
 
 namespace {
@@ -41,14 +54,34 @@ __device__ __forceinline__ float row16_sum(float v) {
   return v;
 }
 
+template <int CTRL>
+__device__ __forceinline__ int dpp_max(int v) {
+  const int t = __builtin_amdgcn_update_dpp(0, v, CTRL, 0xF, 0xF, true);
+  return v > t ? v : t;
+}
+// max of a non-negative value over the 64 lanes of the wave, as a scalar: the DPP steps of row16_sum,
+// then one lane of each of the 4 rows
+__device__ __forceinline__ int wave_max(int v) {
+  v = dpp_max<0xB1>(v);
+  v = dpp_max<0x4E>(v);
+  v = dpp_max<0x141>(v);
+  v = dpp_max<0x140>(v);
+  const int a = __builtin_amdgcn_readlane(v, 0), b = __builtin_amdgcn_readlane(v, 16);
+  const int c = __builtin_amdgcn_readlane(v, 32), d = __builtin_amdgcn_readlane(v, 48);
+  const int ab = a > b ? a : b, cd = c > d ? c : d;
+  return ab > cd ? ab : cd;
+}
+
 __device__ __forceinline__ float fexp2(float x) { return __builtin_amdgcn_exp2f(x); }
 
 // Workspace: acc[B*Hq*nsplit][128] f32, then (m, l)[B*Hq*nsplit] f32 pairs; m in the base-2 domain.
-template <int REP, int KT>
+// DEVGEO: nsplit is the grid's split count (the workspace stride) only, `chunk` is not read, and the
+// live split count and chunk come from kv_len, want and min_keys (header comment).
+template <int REP, int KT, bool DEVGEO>
 __global__ __launch_bounds__(256) void decode_attn_kernel(
     const ushort* __restrict__ q, const ushort* __restrict__ kc, const ushort* __restrict__ vc,
     const int* __restrict__ kv_len, float* __restrict__ ws, int Hq, int Hkv, int Smax, long stride_b,
-    long stride_h, int nsplit, int chunk, int extra, float qscale) {
+    long stride_h, int nsplit, int chunk, int extra, float qscale, int want, int min_keys) {
   const int split = blockIdx.x, hkv = blockIdx.y, b = blockIdx.z;
   const int B = gridDim.z;
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
@@ -60,10 +93,26 @@ __global__ __launch_bounds__(256) void decode_attn_kernel(
 
   long len = (long)kv_len[b] + extra;
   len = len < 0 ? 0 : (len > Smax ? Smax : len);  // before any address is formed
+  int ns_eff = nsplit;
+  if constexpr (DEVGEO) {
+    int longest = 0;
+    for (int i = lane; i < B; i += 64) {
+      long n = (long)kv_len[i] + extra;
+      n = n < 0 ? 0 : (n > Smax ? Smax : n);
+      longest = longest > (int)n ? longest : (int)n;
+    }
+    longest = wave_max(longest);  // a scalar: the geometry below stays in SGPRs
+    ns_eff = (int)((unsigned)longest / (unsigned)min_keys);
+    ns_eff = ns_eff < want ? ns_eff : want;
+    ns_eff = ns_eff < nsplit ? ns_eff : nsplit;  // the last live split must be in the grid
+    ns_eff = ns_eff > 1 ? ns_eff : 1;
+    chunk = (int)((unsigned)(longest + ns_eff - 1) / (unsigned)ns_eff);
+    chunk = chunk > 1 ? chunk : 1;
+  }
   const long start = (long)split * chunk;
-  long end = split == nsplit - 1 ? len : start + chunk;
+  long end = split == ns_eff - 1 ? len : start + chunk;
   end = end > len ? len : end;
-  if (start >= end) {  // nothing to read: the neutral element
+  if ((DEVGEO && split >= ns_eff) || start >= end) {  // nothing to read: the neutral element
     for (int i = tid; i < REP * DH; i += 256) ws_acc[(part0 + (long)(i >> 7) * nsplit) * DH + (i & 127)] = 0.f;
     if (tid < REP) {
       ws_ml[(part0 + (long)tid * nsplit) * 2] = -INFINITY;
@@ -291,20 +340,20 @@ extern "C" int th_decode_rope_append(const void* qkv, const int* pos, const floa
   TH_CHECK_LAUNCH();
 }
 
-// ws: B * Hq * nsplit * 130 floats.  Keys [split * chunk, +chunk) go to split `split` (the last one
-// takes the rest); kv_len[b] + extra keys are valid, clamped to [0, Smax] on the device.
-extern "C" int th_decode_attn(const void* q, const void* kcache, const void* vcache, const int* kv_len,
-                              void* o, float* ws, int B, int Hq, int Hkv, int Dh, int Smax,
-                              long stride_b, long stride_h, int nsplit, int chunk, int extra,
-                              float scale, hipStream_t s) {
-  if (!cache_geometry_ok(B, Hq, Hkv, Dh, Smax, stride_b, stride_h)) return -1;
-  if (nsplit <= 0 || nsplit > 1024 || chunk <= 0 || (long)nsplit * chunk > (1L << 30)) return -1;
+namespace {
+
+template <bool DEVGEO>
+int launch_decode_attn(const void* q, const void* kcache, const void* vcache, const int* kv_len, void* o,
+                       float* ws, int B, int Hq, int Hkv, int Smax, long stride_b, long stride_h,
+                       int nsplit, int chunk, int extra, float scale, int want, int min_keys,
+                       hipStream_t s) {
   const dim3 grid(nsplit, Hkv, B);
   const float qscale = scale * 1.4426950408889634f;  // scores in the base-2 domain
   const ushort *qp = (const ushort*)q, *kp = (const ushort*)kcache, *vp = (const ushort*)vcache;
-#define TH_DECODE_LAUNCH(REP, KT)                                                               \
-  decode_attn_kernel<REP, KT><<<grid, 256, 0, s>>>(qp, kp, vp, kv_len, ws, Hq, Hkv, Smax,       \
-                                                   stride_b, stride_h, nsplit, chunk, extra, qscale)
+#define TH_DECODE_LAUNCH(REP, KT)                                                                      \
+  decode_attn_kernel<REP, KT, DEVGEO><<<grid, 256, 0, s>>>(qp, kp, vp, kv_len, ws, Hq, Hkv, Smax,      \
+                                                           stride_b, stride_h, nsplit, chunk, extra,   \
+                                                           qscale, want, min_keys)
   switch (Hq / Hkv) {
     case 1: TH_DECODE_LAUNCH(1, 8); break;
     case 2: TH_DECODE_LAUNCH(2, 8); break;
@@ -316,4 +365,30 @@ extern "C" int th_decode_attn(const void* q, const void* kcache, const void* vca
   if (e != hipSuccess) return (int)e;
   decode_combine_kernel<<<B * Hq, 128, 0, s>>>(ws, (ushort*)o, (long)B * Hq * nsplit, nsplit);
   TH_CHECK_LAUNCH();
+}
+
+}  // namespace
+
+// ws: B * Hq * nsplit * 130 floats.  Keys [split * chunk, +chunk) go to split `split` (the last one
+// takes the rest); kv_len[b] + extra keys are valid, clamped to [0, Smax] on the device.
+extern "C" int th_decode_attn(const void* q, const void* kcache, const void* vcache, const int* kv_len,
+                              void* o, float* ws, int B, int Hq, int Hkv, int Dh, int Smax,
+                              long stride_b, long stride_h, int nsplit, int chunk, int extra,
+                              float scale, hipStream_t s) {
+  if (!cache_geometry_ok(B, Hq, Hkv, Dh, Smax, stride_b, stride_h)) return -1;
+  if (nsplit <= 0 || nsplit > 1024 || chunk <= 0 || (long)nsplit * chunk > (1L << 30)) return -1;
+  return launch_decode_attn<false>(q, kcache, vcache, kv_len, o, ws, B, Hq, Hkv, Smax, stride_b, stride_h,
+                                   nsplit, chunk, extra, scale, 0, 1, s);
+}
+
+// The same with the geometry taken from kv_len on the device (header comment): the grid and the
+// workspace (B * Hq * nsplit_cap * 130 floats) are fixed by nsplit_cap, whatever the lengths become.
+extern "C" int th_decode_attn_dev(const void* q, const void* kcache, const void* vcache, const int* kv_len,
+                                  void* o, float* ws, int B, int Hq, int Hkv, int Dh, int Smax,
+                                  long stride_b, long stride_h, int nsplit_cap, int want, int min_keys,
+                                  int extra, float scale, hipStream_t s) {
+  if (!cache_geometry_ok(B, Hq, Hkv, Dh, Smax, stride_b, stride_h)) return -1;
+  if (nsplit_cap <= 0 || nsplit_cap > 1024 || want <= 0 || min_keys <= 0) return -1;
+  return launch_decode_attn<true>(q, kcache, vcache, kv_len, o, ws, B, Hq, Hkv, Smax, stride_b, stride_h,
+                                  nsplit_cap, 0, extra, scale, want, min_keys, s);
 }

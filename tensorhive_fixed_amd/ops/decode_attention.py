@@ -10,7 +10,10 @@ and may hold anything.
 k and v into cache row ``lens[b]`` and returns the rotated q ``[B, Hq*128]``.  It does not advance
 the lengths: every layer appends at the same row, then the model calls ``cache.advance()``.
 ``decode_attention(q, cache, layer, nsplit=None, new=0)`` attends over the first ``lens[b] + new``
-rows (``new=1`` right after ``rope_append``).
+rows (``new=1`` right after ``rope_append``).  Its split geometry comes from the host lengths; with
+``device_geometry=True`` the kernel derives it from ``lens_dev`` under a grid sized for ``max_len``
+(``device_split_geometry`` is that rule), so the launch can be captured into a graph and replayed
+while the lengths grow, with the same bits as the host rule gives.
 
 GPU tensors run the gfx950 kernels (a missing entry point raises, there is no SDPA fallback);
 CPU tensors run the fp32 reference below, which is also the tests' oracle.
@@ -71,7 +74,15 @@ class KVCache:
         self.lens = [x + n for x in self.lens]
         self.lens_dev += n
 
+    def advance_host(self, n: int = 1) -> None:
+        """Advance the host list only: for a captured step, whose replay advanced ``lens_dev`` itself."""
+        if max(self.lens) + n > self.max_len:
+            raise ValueError(f"KVCache: {max(self.lens)} + {n} rows exceed max_len {self.max_len}")
+        self.lens = [x + n for x in self.lens]
+
     def workspace(self, floats: int) -> torch.Tensor:
+        """At least ``floats`` f32 of scratch.  A larger request replaces the buffer and never touches
+        the old one: whoever captured its address into a graph keeps a reference to it."""
         if self._ws is None or self._ws.numel() < floats:
             self._ws = torch.empty(floats, device=self.device, dtype=torch.float32)
         return self._ws
@@ -147,16 +158,47 @@ def pick_nsplit(batch: int, n_kv_heads: int, max_kv_len: int, n_cus: int) -> int
     return max(1, min(want, max_kv_len // MIN_KEYS_PER_SPLIT, MAX_SPLITS))
 
 
+def device_split_geometry(lens, new: int, want: int, max_len: int, min_keys: int = MIN_KEYS_PER_SPLIT,
+                          cap: int = MAX_SPLITS) -> tuple[int, int]:
+    """``(ns_eff, chunk)`` as the ``device_geometry`` kernel derives them from the device lengths:
+    the rule of ``pick_nsplit`` on the longest sequence, then ``decode_attention``'s ``chunk``.  ``want``
+    is ``ceil(CUs / (batch * n_kv_heads))``; ``cap`` is the grid's split count, ``pick_nsplit`` at
+    ``max_len`` (never above ``MAX_SPLITS``, and never below what the rule picks at a shorter length).
+    A forced split count passes ``want = cap = nsplit`` and ``min_keys = 1``."""
+    longest = max(min(max(int(n) + new, 0), max_len) for n in lens)
+    ns_eff = max(1, min(want, longest // min_keys, cap))
+    return ns_eff, max(1, -(-longest // ns_eff))
+
+
 def decode_attention(q: torch.Tensor, cache: KVCache, layer: int, nsplit: int | None = None,
-                     new: int = 0) -> torch.Tensor:
+                     new: int = 0, device_geometry: bool = False) -> torch.Tensor:
     """``q [B, Hq*128]`` against the first ``lens[b] + new`` rows of ``layer`` -> ``o [B, Hq*128]``.
-    ``nsplit`` overrides the automatic split count (tests)."""
+    ``nsplit`` overrides the automatic split count (tests).  ``device_geometry`` takes the split count
+    and chunk from ``lens_dev`` inside the kernel (``device_split_geometry``) under a grid of
+    ``pick_nsplit`` at ``max_len`` splits, or of ``nsplit`` where given; nothing the launch is given then
+    depends on the current lengths, and the output has the bits of the host rule."""
     Hq, Hkv = cache.n_heads, cache.n_kv_heads
     _check(q, cache, Hq * HEAD_DIM, layer, new, "decode_attention")
     if nsplit is not None and not 1 <= int(nsplit) <= 1024:
         raise ValueError("decode_attention: nsplit must be in [1, 1024]")
     if not q.is_cuda:
         return decode_attention_reference(q, cache, layer, new)
+    if device_geometry:
+        if nsplit is None:
+            cus = torch.cuda.get_device_properties(q.device).multi_processor_count
+            want = -(-cus // (cache.batch * Hkv))
+            cap, min_keys = pick_nsplit(cache.batch, Hkv, cache.max_len, cus), MIN_KEYS_PER_SPLIT
+        else:
+            want = cap = int(nsplit)
+            min_keys = 1
+        o = torch.empty_like(q)
+        ws = cache.workspace(cache.batch * Hq * cap * (HEAD_DIM + 2))
+        kc, vc = cache.k(layer), cache.v(layer)
+        _lib.call("th_decode_attn_dev", q.data_ptr(), kc.data_ptr(), vc.data_ptr(), cache.lens_dev.data_ptr(),
+                  o.data_ptr(), ws.data_ptr(), cache.batch, Hq, Hkv, HEAD_DIM, cache.max_len, kc.stride(0),
+                  kc.stride(1), cap, want, min_keys, int(new), 1.0 / math.sqrt(HEAD_DIM),
+                  _lib.stream_ptr(q.device))
+        return o
     longest = max(cache.lens) + new
     if nsplit is None:
         cus = torch.cuda.get_device_properties(q.device).multi_processor_count

@@ -4,8 +4,11 @@ tokens with the KV cache and the split-KV decode attention kernel (``ops/decode_
 Launched like the training payload, one process on one GPU (``python -m
 tensorhive_fixed_amd.workloads.llama3_generate``), typically as a task of the tensorhive job queue.
 It prints ``[th-gen] step=N tokens/s=X batch=B`` lines and ends with one JSON line
-``{"event": "done", "new_tokens": ..., "prefill_ms": ..., "decode_ms_per_token": ..., "stream_gemm": ...}``.
-``--stream-gemm`` runs the decode steps' GEMMs on the weight-streaming kernel of ``ops/decode_linear.py``.
+``{"event": "done", "new_tokens": ..., "prefill_ms": ..., "decode_ms_per_token": ..., "stream_gemm": ...,
+"graph": ...}``.
+``--stream-gemm`` runs the decode steps' GEMMs on the weight-streaming kernel of ``ops/decode_linear.py``;
+``--graph`` captures the decode step once and replays it for every token (``models/decode_graph.py``;
+the capture happens right after the prefill and is counted in ``prefill_ms``).  The two compose.
 
 The project has no tokenizer: prompts are token ids, from ``--prompt-ids FILE`` (a JSON list of id
 lists, which may be ragged) or synthetic ones drawn like the training data.
@@ -79,6 +82,8 @@ def main(argv: list[str] | None = None) -> int:
     ap.add_argument("--device", default=None, help="default: cuda when available, else cpu")
     ap.add_argument("--stream-gemm", action="store_true",
                     help="decode steps run their GEMMs on the weight-streaming kernel (ops/decode_linear.py)")
+    ap.add_argument("--graph", action="store_true",
+                    help="capture the decode step into a graph and replay it per token (models/decode_graph.py)")
     args = ap.parse_args(argv)
     from ..utils.blas_env import refuse_unsafe_blas_workspace
 
@@ -110,13 +115,15 @@ def main(argv: list[str] | None = None) -> int:
             marks["last"], marks["last_step"] = now, i
 
     ids = model.generate(tokens, lens, max_new_tokens=args.max_new_tokens, temperature=args.temperature,
-                         top_k=args.top_k, generator=sampler, on_step=on_step, stream_gemm=args.stream_gemm)
+                         top_k=args.top_k, generator=sampler, on_step=on_step, stream_gemm=args.stream_gemm,
+                         graph=args.graph)
     end = sync()
     decode_steps = args.max_new_tokens - 1
     print(json.dumps({"event": "done", "new_tokens": int(ids.numel()),
                       "prefill_ms": round(1000.0 * (marks["prefill"] - marks["t0"]), 3),
                       "decode_ms_per_token": round(1000.0 * (end - marks["prefill"]) / decode_steps, 3)
-                      if decode_steps else None, "stream_gemm": bool(args.stream_gemm)}), flush=True)
+                      if decode_steps else None, "stream_gemm": bool(args.stream_gemm),
+                      "graph": bool(args.graph)}), flush=True)
     return 0
 
 
