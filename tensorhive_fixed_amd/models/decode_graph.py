@@ -8,7 +8,7 @@ depends on the current lengths: RoPE + append and the attention read ``cache.len
 device, and the attention derives its split geometry there too (``decode_attention(...,
 device_geometry=True)``), under a grid sized for ``cache.max_len``.  Its partials are those of the
 host rule, so a replayed step has the bits of the eager step wherever the GEMMs are the project's own
-kernels (``stream_gemm``).
+kernels (``stream_gemm``, or ``fp8``: the step on FP8 weights, where all of them are).
 
 The graph reads the cache, ``lens_dev`` and the weights through fixed addresses, so it stays valid
 after ``cache.set_lens`` or another ``prefill`` into the same cache; the weights must not be
@@ -28,7 +28,7 @@ from ..ops.decode_attention import KVCache
 class DecodeGraph:
     """``step(tokens [B]) -> logits [B, vocab] f32`` on top of ``cache``; built by ``Llama.decode_graph``."""
 
-    def __init__(self, model, cache: KVCache, stream_gemm: bool = False):
+    def __init__(self, model, cache: KVCache, stream_gemm: bool = False, fp8: bool = False):
         model._need_add_norm("decode_graph")
         if cache.cfg != model.cfg:
             raise ValueError("decode_graph: the cache was built for another model configuration")
@@ -37,8 +37,12 @@ class DecodeGraph:
         if max(cache.lens) >= cache.max_len:
             raise ValueError(f"decode_graph: the cache is full ({max(cache.lens)} of {cache.max_len} rows): "
                              "no dead row to warm up on")
-        self.model, self.cache, self.stream_gemm = model, cache, bool(stream_gemm)
-        self._body = model._decode_step_stream if self.stream_gemm else model._decode_step_plain
+        self.model, self.cache, self.stream_gemm, self.fp8 = model, cache, bool(stream_gemm), bool(fp8)
+        if self.fp8:  # takes precedence, as in decode_step; the FP8 weights must not be re-quantized while it lives
+            model._need_fp8(cache.batch)
+            self._body = model._decode_step_fp8
+        else:
+            self._body = model._decode_step_stream if self.stream_gemm else model._decode_step_plain
         self._graph = None
         if cache.device.type == "cuda":
             self._capture()
@@ -76,7 +80,7 @@ class DecodeGraph:
             raise ValueError(f"DecodeGraph.step: {max(cache.lens)} + 1 rows exceed the cache's max_len "
                              f"{cache.max_len}")
         if self._graph is None:
-            return self.model.decode_step(tokens, cache, stream_gemm=self.stream_gemm)
+            return self.model.decode_step(tokens, cache, stream_gemm=self.stream_gemm, fp8=self.fp8)
         self._tokens.copy_(tokens)
         self._graph.replay()
         cache.advance_host(1)  # the replay advanced lens_dev

@@ -31,6 +31,7 @@ from ..ops.cross_entropy import linear_cross_entropy
 from ..ops.decode_attention import KVCache, decode_attention, rope_append
 from ..ops.decode_linear import decode_gate_up_swiglu, decode_linear
 from ..ops.decode_linear import preferred as dl_preferred
+from ..ops.decode_linear_fp8 import decode_gate_up_swiglu_fp8, decode_linear_fp8, quantize_weight_fp8, supported_fp8
 from ..ops.embedding import embedding
 from ..ops.linear import linear
 from ..ops.mlp import gate_up_swiglu
@@ -156,6 +157,9 @@ class Llama(nn.Module):
         # ZeRO-1 hook: called with the parameters about to be read, so a sharded store can make the
         # stream wait for exactly the all-gather buckets holding them (parallel/flat.py)
         self.param_gate = None
+        # (wq, scale) pairs of the decode-step weights, built by quantize_decode_weights(); a plain
+        # attribute holding plain tensors: no Parameter, no buffer, invisible to state_dict()
+        self.fp8_weights = None
         self.reset_parameters(seed)
 
     @torch.no_grad()
@@ -257,15 +261,20 @@ class Llama(nn.Module):
         return rmsnorm_add_fork(pending[rows].contiguous(), x[rows].contiguous(), self.norm, c.norm_eps)[0]
 
     @torch.no_grad()
-    def decode_step(self, tokens: torch.Tensor, cache: KVCache, stream_gemm: bool = False) -> torch.Tensor:
+    def decode_step(self, tokens: torch.Tensor, cache: KVCache, stream_gemm: bool = False,
+                    fp8: bool = False) -> torch.Tensor:
         """One new token per sequence (``tokens [B]``) on top of ``cache`` -> f32 logits ``[B, vocab]``;
         advances the cache lengths by one.  ``stream_gemm`` runs the projections and the LM head on the
-        weight-streaming kernel of ``ops/decode_linear.py`` wherever its ``preferred`` allows."""
+        weight-streaming kernel of ``ops/decode_linear.py`` wherever its ``preferred`` allows.  ``fp8``
+        (which takes precedence) runs all of them on the FP8 weights of ``quantize_decode_weights()``
+        with ``ops/decode_linear_fp8.py``; it raises when they are missing or the batch is above 16."""
         self._need_add_norm("decode_step")
         c = self.cfg
         B = tokens.shape[0]
         if tokens.dim() != 1 or B != cache.batch:
             raise ValueError(f"decode_step: expected {cache.batch} token ids, got shape {tuple(tokens.shape)}")
+        if fp8:
+            return self._decode_step_fp8(tokens, cache)
         if stream_gemm:
             return self._decode_step_stream(tokens, cache)
         return self._decode_step_plain(tokens, cache)
@@ -332,12 +341,64 @@ class Llama(nn.Module):
         return torch.mm(h, self.lm_head.t()).float()
 
     @torch.no_grad()
-    def decode_graph(self, cache: KVCache, stream_gemm: bool = False):
+    def quantize_decode_weights(self) -> None:
+        """Build and keep the FP8 form (``ops/decode_linear_fp8.quantize_weight_fp8``: e4m3 codes and one
+        f32 scale per output row) of every layer's ``wqkv``, ``wo``, ``w13`` and ``w2`` and of ``lm_head``,
+        for ``decode_step(fp8=True)``.  The bf16 parameters stay (the prefill runs on them), so this adds
+        half their bytes.  Call it again after the parameters change, e.g. after a checkpoint load: the
+        FP8 copies do not follow them.  A weight shape the FP8 kernel does not take raises here."""
+        ws = [(f"layers.{i}.{n}", getattr(blk, n)) for i, blk in enumerate(self.layers)
+              for n in ("wqkv", "wo", "w13", "w2")] + [("lm_head", self.lm_head)]
+        for name, w in ws:
+            if not supported_fp8(1, w.shape[0], w.shape[1]):
+                raise ValueError(f"quantize_decode_weights: {name} {tuple(w.shape)} is outside the FP8 decode "
+                                 "kernel's shape rule (ops/decode_linear_fp8.supported_fp8)")
+        q = {name: quantize_weight_fp8(w.detach().contiguous()) for name, w in ws}
+        self.fp8_weights = {"layers": [{n: q[f"layers.{i}.{n}"] for n in ("wqkv", "wo", "w13", "w2")}
+                                       for i in range(len(self.layers))], "lm_head": q["lm_head"]}
+
+    def _need_fp8(self, B: int) -> dict:
+        if self.fp8_weights is None:
+            raise ValueError("decode_step(fp8=True): call quantize_decode_weights() first")
+        if B > 16:
+            raise ValueError(f"decode_step(fp8=True): batch {B} is above the 16 rows of the FP8 decode kernel "
+                             "(there is no other FP8 path to take)")
+        return self.fp8_weights
+
+    def _decode_step_fp8(self, tokens: torch.Tensor, cache: KVCache, device_geometry: bool = False,
+                         advance=None) -> torch.Tensor:
+        """``decode_step`` with all five GEMMs on the FP8 weights (``ops/decode_linear_fp8.py``): gate|up
+        and SwiGLU in one call, f32 logits from the f32 accumulator.  No shape falls back to the bf16
+        weights, so the numerics do not depend on the batch size.  ``device_geometry`` and ``advance``
+        as in ``_decode_step_plain``."""
+        c = self.cfg
+        B = tokens.shape[0]
+        fw = self._need_fp8(B)
+        x = embedding(tokens.view(B, 1), self.tok_emb).view(B, c.dim)
+        pending = None
+        for i, (blk, q) in enumerate(zip(self.layers, fw["layers"])):
+            if pending is None:
+                h, x = _norm(x, blk.attn_norm, c.norm_eps)
+            else:
+                h, x = rmsnorm_add_fork(pending, x, blk.attn_norm, c.norm_eps)
+            qv = rope_append(decode_linear_fp8(h, *q["wqkv"]), cache, i)
+            o = decode_attention(qv, cache, i, new=1, device_geometry=device_geometry)
+            h, x = rmsnorm_add_fork(decode_linear_fp8(o, *q["wo"]), x, blk.ffn_norm, c.norm_eps)
+            pending = decode_linear_fp8(decode_gate_up_swiglu_fp8(h, *q["w13"]), *q["w2"])
+        if advance is None:
+            cache.advance(1)
+        else:
+            advance()
+        h = rmsnorm_add_fork(pending, x, self.norm, c.norm_eps)[0]
+        return decode_linear_fp8(h, *fw["lm_head"], out_dtype=torch.float32)
+
+    @torch.no_grad()
+    def decode_graph(self, cache: KVCache, stream_gemm: bool = False, fp8: bool = False):
         """``decode_step`` on ``cache`` captured into a graph (``models/decode_graph.py``): the returned
         object's ``step(tokens)`` replays it with one launch per token.  On the CPU it runs the eager step."""
         from .decode_graph import DecodeGraph
 
-        return DecodeGraph(self, cache, stream_gemm=stream_gemm)
+        return DecodeGraph(self, cache, stream_gemm=stream_gemm, fp8=fp8)
 
     @staticmethod
     def sample(logits: torch.Tensor, temperature: float = 0.0, top_k: int | None = None,
@@ -356,13 +417,15 @@ class Llama(nn.Module):
     def generate(self, tokens: torch.Tensor, prompt_lens=None, max_new_tokens: int = 16,
                  temperature: float = 0.0, top_k: int | None = None,
                  generator: torch.Generator | None = None, return_logits: bool = False,
-                 on_step=None, stream_gemm: bool = False, graph: bool = False):
+                 on_step=None, stream_gemm: bool = False, graph: bool = False, fp8: bool = False):
         """Continue the left-aligned prompts ``tokens [B, S]`` (``prompt_lens`` defaults to ``S`` for all)
         by ``max_new_tokens`` tokens -> ids ``[B, max_new_tokens]`` (and the f32 logits
         ``[B, max_new_tokens, vocab]`` of every step with ``return_logits``).  ``on_step(i)`` is called
         after step ``i``'s token is chosen (step 0 comes from the prefill).  ``stream_gemm`` is passed to
         every ``decode_step``; the prefill is the same either way.  ``graph`` captures the decode step
-        once after the prefill (``decode_graph``) and replays it for every further token."""
+        once after the prefill (``decode_graph``) and replays it for every further token.  ``fp8`` runs
+        the decode steps on FP8 weights (``decode_step(fp8=True)``), quantizing them first if
+        ``quantize_decode_weights()`` has not been called; the prefill stays on the bf16 weights."""
         B, S = tokens.shape
         lens = [S] * B if prompt_lens is None else [int(n) for n in prompt_lens]
         if max_new_tokens < 1:
@@ -373,6 +436,10 @@ class Llama(nn.Module):
         if max_len > self.cfg.max_seq_len:
             raise ValueError(f"generate: {S} prompt + {max_new_tokens} new tokens exceed max_seq_len "
                              f"{self.cfg.max_seq_len}")
+        if fp8:
+            if self.fp8_weights is None:
+                self.quantize_decode_weights()
+            self._need_fp8(B)  # before the prefill, not after it
         cache = KVCache(self.cfg, B, max_len, tokens.device)
         if len(lens) != B or min(lens) < 1 or S > tokens.shape[1]:
             raise ValueError(f"generate: prompt lengths {lens} do not fit tokens of shape {tuple(tokens.shape)}")
@@ -381,13 +448,14 @@ class Llama(nn.Module):
         padded[:, :S] = tokens[:, :S] * live  # token 0 after every prompt
         h = self.prefill(padded, lens, cache)
         logits = torch.mm(h, self.lm_head.t()).float()
-        captured = self.decode_graph(cache, stream_gemm=stream_gemm) if graph and max_new_tokens > 1 else None
+        captured = (self.decode_graph(cache, stream_gemm=stream_gemm, fp8=fp8)
+                    if graph and max_new_tokens > 1 else None)
         out, steps = [], []
         for i in range(max_new_tokens):
             if i and captured is not None:
                 logits = captured.step(out[-1])
             elif i:
-                logits = self.decode_step(out[-1], cache, stream_gemm=stream_gemm)
+                logits = self.decode_step(out[-1], cache, stream_gemm=stream_gemm, fp8=fp8)
             out.append(self.sample(logits, temperature, top_k, generator))
             if return_logits:
                 steps.append(logits.clone() if captured is not None else logits)  # a replay reuses its output

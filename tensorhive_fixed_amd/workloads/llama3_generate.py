@@ -5,10 +5,13 @@ Launched like the training payload, one process on one GPU (``python -m
 tensorhive_fixed_amd.workloads.llama3_generate``), typically as a task of the tensorhive job queue.
 It prints ``[th-gen] step=N tokens/s=X batch=B`` lines and ends with one JSON line
 ``{"event": "done", "new_tokens": ..., "prefill_ms": ..., "decode_ms_per_token": ..., "stream_gemm": ...,
-"graph": ...}``.
+"graph": ..., "fp8_weights": ..., "quantize_ms": ...}``.
 ``--stream-gemm`` runs the decode steps' GEMMs on the weight-streaming kernel of ``ops/decode_linear.py``;
 ``--graph`` captures the decode step once and replays it for every token (``models/decode_graph.py``;
 the capture happens right after the prefill and is counted in ``prefill_ms``).  The two compose.
+``--fp8-weights`` quantizes the decode-step weights to FP8 after the checkpoint load (``quantize_ms``, not
+counted in ``prefill_ms``) and runs every decode-step GEMM on them (``ops/decode_linear_fp8.py``, batch <= 16);
+it composes with ``--graph`` and takes precedence over ``--stream-gemm``.
 
 The project has no tokenizer: prompts are token ids, from ``--prompt-ids FILE`` (a JSON list of id
 lists, which may be ragged) or synthetic ones drawn like the training data.
@@ -84,6 +87,9 @@ def main(argv: list[str] | None = None) -> int:
                     help="decode steps run their GEMMs on the weight-streaming kernel (ops/decode_linear.py)")
     ap.add_argument("--graph", action="store_true",
                     help="capture the decode step into a graph and replay it per token (models/decode_graph.py)")
+    ap.add_argument("--fp8-weights", action="store_true",
+                    help="decode steps run on FP8 (e4m3, per-row scale) copies of the weights "
+                         "(ops/decode_linear_fp8.py); the prefill stays on bf16")
     args = ap.parse_args(argv)
     from ..utils.blas_env import refuse_unsafe_blas_workspace
 
@@ -103,6 +109,11 @@ def main(argv: list[str] | None = None) -> int:
             torch.cuda.synchronize(device)
         return time.perf_counter()
 
+    quantize_ms = None
+    if args.fp8_weights:
+        t = sync()
+        model.quantize_decode_weights()
+        quantize_ms = round(1000.0 * (sync() - t), 3)
     marks = {"t0": sync(), "last": None, "last_step": 0}
 
     def on_step(i: int) -> None:
@@ -116,14 +127,15 @@ def main(argv: list[str] | None = None) -> int:
 
     ids = model.generate(tokens, lens, max_new_tokens=args.max_new_tokens, temperature=args.temperature,
                          top_k=args.top_k, generator=sampler, on_step=on_step, stream_gemm=args.stream_gemm,
-                         graph=args.graph)
+                         graph=args.graph, fp8=args.fp8_weights)
     end = sync()
     decode_steps = args.max_new_tokens - 1
     print(json.dumps({"event": "done", "new_tokens": int(ids.numel()),
                       "prefill_ms": round(1000.0 * (marks["prefill"] - marks["t0"]), 3),
                       "decode_ms_per_token": round(1000.0 * (end - marks["prefill"]) / decode_steps, 3)
                       if decode_steps else None, "stream_gemm": bool(args.stream_gemm),
-                      "graph": bool(args.graph)}), flush=True)
+                      "graph": bool(args.graph), "fp8_weights": bool(args.fp8_weights),
+                      "quantize_ms": quantize_ms}), flush=True)
     return 0
 
 
