@@ -179,7 +179,8 @@ def gemm_tn_(a: torch.Tensor, b: torch.Tensor, out: torch.Tensor, accumulate: bo
         return out
     tiles = (M // _TILE) * (N // _TILE)
     if splitk is None and mode == 10:
-        sk, full = tn_plan(M, N, K)
+        # an output below one tile has nothing to plan (the model divides by the tile count): torch.mm below
+        sk, full = tn_plan(M, N, K) if tiles else (1, 0)
     elif splitk is None:
         sk, full = 1, tiles
     else:
