@@ -1,8 +1,10 @@
 #!/usr/bin/env python3
 """Render the tables of profiles/attention_accuracy/README.md from the figures one run of
-tests/gpu/test_attention_profiles_gpu.py leaves under TH_ATTN_ACCURACY_JSON.
+tests/gpu/test_attention_profiles_gpu.py and tests/gpu/test_flash_tails_gpu.py leaves under
+TH_ATTN_ACCURACY_JSON (the tails file adds its figures to the file under "tails").
 
-    TH_ATTN_ACCURACY_JSON=acc.json python -m pytest tests/gpu/test_attention_profiles_gpu.py
+    TH_ATTN_ACCURACY_JSON=acc.json python -m pytest tests/gpu/test_attention_profiles_gpu.py \\
+        tests/gpu/test_flash_tails_gpu.py
     python scripts/attention_accuracy_table.py acc.json
 """
 import json
@@ -12,8 +14,47 @@ FLAGS = ("kf_default", "kh", "fused_dkv", "regstage")
 PROFILES = ("randn", "ramp_up", "ramp_down", "sink", "step", "mixed_rows", "rising_spikes", "large")
 
 
+def tails(rec: dict) -> None:
+    """Worst ratio to E_b per length, mask and flag set over both profiles and batch entries, and the worst
+    share of the lse tolerance over both forwards.  S = 1 has E_b = 0 for o, dq and dk (own bounds): '-'."""
+    cells: dict = {}
+    for key, vals in rec["flash"].items():
+        S, _, mask, flag = key.split("|")[:4]
+        cell = cells.setdefault((int(S[1:]), mask), {}).setdefault(flag, {})
+        for n, r in vals.items():
+            cell[n] = max(cell.get(n, 0.0), r)
+    for key, vals in rec["rope"].items():
+        S, _, mask, flag = key.split("|")[:4]
+        cell = cells.setdefault((int(S[1:]), mask), {}).setdefault("rope " + flag, {})
+        for n, r in vals.items():
+            cell[n] = max(cell.get(n, 0.0), r)
+    lse: dict = {}
+    for key, (_, share) in rec["lse"].items():
+        S, _, mask = key.split("|")[:3]
+        lse[(int(S[1:]), mask)] = max(lse.get((int(S[1:]), mask), 0.0), share)
+    bwd = ("kh", "fused_dkv", "regstage")
+    rope = ("rope kf_default", "rope kh")
+
+    def show(cell, names):
+        return " / ".join(f"{cell[n]:.2f}" if n in cell else "-" for n in names) if cell else ""
+
+    print("| S | mask | o fwd / fwd_regstage | lse (of tolerance) | " + " | ".join(f"{f} dq / dk / dv" for f in bwd)
+          + " | " + " | ".join(f"{f} dq / dk" for f in rope) + " |")
+    print("|---|---|---|---|" + "---|" * (len(bwd) + len(rope)))
+    for (S, mask), row in sorted(cells.items()):
+        o = " / ".join(f"{row[f]['o']:.2f}" if "o" in row.get(f, {}) else "-" for f in ("fwd", "fwd_regstage"))
+        print(f"| {S} | {mask} | {o} | {lse[(S, mask)]:.2f} | "
+              + " | ".join(show(row.get(f), ("dq", "dk", "dv")) for f in bwd) + " | "
+              + " | ".join(show(row.get(f), ("dq", "dk")) for f in rope) + " |")
+    print()
+
+
 def main(path: str) -> None:
     rec = json.load(open(path))
+    if "tails" in rec:
+        tails(rec["tails"])
+    if "flash" not in rec:
+        return
     flash: dict = {}
     for key, vals in rec["flash"].items():  # the same profile in batch slot 0 and 1 of a shape: keep the worse
         profile, shape, mask, flag = key.split("|")[:4]

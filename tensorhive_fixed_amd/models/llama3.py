@@ -431,8 +431,7 @@ class Llama(nn.Module):
         if max_new_tokens < 1:
             raise ValueError("generate: max_new_tokens must be at least 1")
         S = max(lens) if lens else S
-        pad = -(-S // 64) * 64  # the flash forward at lengths its own tests cover
-        max_len = max(pad, S + max_new_tokens)
+        max_len = S + max_new_tokens  # the prefill runs at max(lens), unpadded (tests/gpu/test_flash_tails_gpu.py)
         if max_len > self.cfg.max_seq_len:
             raise ValueError(f"generate: {S} prompt + {max_new_tokens} new tokens exceed max_seq_len "
                              f"{self.cfg.max_seq_len}")
@@ -443,10 +442,8 @@ class Llama(nn.Module):
         cache = KVCache(self.cfg, B, max_len, tokens.device)
         if len(lens) != B or min(lens) < 1 or S > tokens.shape[1]:
             raise ValueError(f"generate: prompt lengths {lens} do not fit tokens of shape {tuple(tokens.shape)}")
-        padded = torch.zeros((B, pad), device=tokens.device, dtype=tokens.dtype)
         live = torch.arange(S, device=tokens.device)[None, :] < torch.tensor(lens, device=tokens.device)[:, None]
-        padded[:, :S] = tokens[:, :S] * live  # token 0 after every prompt
-        h = self.prefill(padded, lens, cache)
+        h = self.prefill(tokens[:, :S] * live, lens, cache)  # token 0 after every prompt
         logits = torch.mm(h, self.lm_head.t()).float()
         captured = (self.decode_graph(cache, stream_gemm=stream_gemm, fp8=fp8)
                     if graph and max_new_tokens > 1 else None)

@@ -217,7 +217,7 @@ def _tiny_pair():
 
 
 def _teacher_forced(model, tokens, lens, steps, step):
-    """Incremental logits [B, 1 + steps, vocab]: bf16 prefill (padded to 64 as ``generate`` does), then
+    """Incremental logits [B, 1 + steps, vocab]: bf16 prefill (prompts zero-padded to 64 columns), then
     ``step(next_tokens, cache)`` per position."""
     from tensorhive_fixed_amd.ops.decode_attention import KVCache
 

@@ -163,7 +163,7 @@ def _tiny_pair():
 
 
 def _teacher_forced(model, tokens, lens, steps):
-    """Incremental logits [B, 1 + steps, vocab] with ``stream_gemm`` (prefill padded to 64 as ``generate`` does)."""
+    """Incremental logits [B, 1 + steps, vocab] with ``stream_gemm`` (prompts zero-padded to 64 columns for the prefill)."""
     from tensorhive_fixed_amd.ops.decode_attention import KVCache
 
     cache = KVCache(model.cfg, tokens.shape[0], 64, tokens.device)

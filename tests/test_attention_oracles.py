@@ -149,3 +149,73 @@ def test_block_max_abs_localises_one_bad_block():
     got[32, 2, 0] = -0.5
     e = ao.block_max_abs(got, ref)
     assert e.shape == (7, 3) and e[6, 1] == 0.25 and e[1, 2] == 0.5 and e.sum() == 0.75
+
+
+# ------------------------------------------------------------------------------------- tail lengths
+TAIL_CASES = [(S, p, causal) for S in ao.TAIL_LENGTHS for p in ao.TAIL_PROFILES for causal in (True, False)]
+
+
+@pytest.mark.parametrize("S,profile,causal", TAIL_CASES,
+                         ids=[f"S{S}-{p}-{'causal' if c else 'full'}" for S, p, c in TAIL_CASES])
+def test_tail_lengths_qualify_for_the_gpu_margin(S, profile, causal):
+    """Every (length, profile, mask) of tests/gpu/test_flash_tails_gpu.py, at the seed of TAIL_SEEDS."""
+    c = ao.tail_case(S, profile, causal)
+    print("E_m / E_b " + "  ".join(f"{n} {c['E_m'][n] / c['E_b'][n]:.2f}" for n in ao.TENSORS if c["E_b"][n] > 0))
+    assert ao.tail_misses(c, S, profile, causal) == []
+    walks = [ao.late_rescales(c["s_log2"][h], causal) for h in range(ao.TAIL_HEADS[0])]
+    if profile == "randn":
+        assert all(fired == 0 for fired, _ in walks), walks
+    elif ao.ramp_must_rescale(S):
+        assert all(fired >= 1 for fired, _ in walks), walks
+    else:  # one tile, or S = 65: the ramp cannot rise by the threshold past tile 0
+        assert all(fired == 0 for fired, _ in walks), walks
+
+
+def test_tail_seeds_are_the_first_that_qualify():
+    for p in ao.TAIL_PROFILES:
+        assert ao.TAIL_SEEDS[p] == {S: ao.first_tail_seed(S, p) for S in ao.TAIL_LENGTHS}, p
+    assert [S for S in ao.TAIL_LENGTHS if S > ao.TILE_KEYS and not ao.ramp_must_rescale(S)] == [65]
+
+
+def test_one_row_is_exact_and_its_cancellation_bounds_hold_for_an_f32_walk():
+    """S = 1: o = v, dq = dk = 0 exactly; dP and delta summed in f32 in two different orders differ by less
+    than the bound on |dS| that ``single_row_bounds`` starts from."""
+    for p in ao.TAIL_PROFILES:
+        c = ao.tail_case(1, p, True)
+        q, k, v, do = (c[n] for n in ("q", "k", "v", "do"))
+        assert torch.equal(c["exact"]["o"], v.double().repeat_interleave(2, 1))
+        assert c["exact"]["dq"].abs().max() == 0 and c["exact"]["dk"].abs().max() == 0
+        if p == "randn":
+            assert 7e-3 < c["E_b"]["dv"] < 9e-3, c["E_b"]["dv"]  # half a bf16 step of |dO| in [2, 4)
+        dq_b, dk_b = ao.single_row_bounds(q, k, v, do)
+        assert dq_b.shape == (1, 4, ao.D) and dk_b.shape == (1, 2, ao.D) and bool((dq_b > 0).all())
+        prod = (do.float() * v.float().repeat_interleave(2, 1))[0]  # [Hq, D]
+        fwd, rev = torch.zeros(4), torch.zeros(4)
+        for d in range(ao.D):
+            fwd, rev = fwd + prod[:, d], rev + prod[:, ao.D - 1 - d]
+        ds_bound = 2 * ao.D * 2.0 ** -24 * prod.double().abs().sum(-1)
+        assert bool(((fwd - rev).double().abs() <= ds_bound).all())
+        want = ds_bound[:, None] * ao.SCALE * k.double().repeat_interleave(2, 1)[0].abs() * (1 + 2.0 ** -8)
+        assert torch.allclose(dq_b[0], want, rtol=1e-12, atol=0)
+
+
+def test_rope_grad_map_is_the_rotary_backward_before_one_rounding():
+    """``grad_map=rope_backward(S)``: exact dq / dk are those of the plain solve turned by rope_oracle's
+    angles (sign -1), dv and o are untouched, and the baseline rounds the rotated value once."""
+    from tests import kernel_oracles as ko
+
+    S, causal = 33, True
+    c = ao.tail_case(S, "randn", causal)
+    q, k, v, do = (c[n] for n in ("q", "k", "v", "do"))
+    turn = ao.rope_backward(S)
+    ex = ao.exact(q, k, v, do, causal, grad_map=turn)
+    packed = torch.cat([c["exact"]["dq"].reshape(S, -1), c["exact"]["dk"].reshape(S, -1)], 1)
+    want, _ = ko.rope_oracle(packed, S, 6, ao.D, ao.ROPE_THETA, -1.0)
+    got = torch.cat([ex["dq"].reshape(S, -1), ex["dk"].reshape(S, -1)], 1)
+    assert (got - want).abs().max().item() <= 1e-12
+    assert torch.equal(ex["dv"], c["exact"]["dv"]) and torch.equal(ex["o"], c["exact"]["o"])
+    base = ao.format_baseline(q, k, v, do, causal, grad_map=turn)
+    for n in ("dq", "dk"):  # one rounding, of the rotated value: a bf16 within half a step of it
+        assert torch.equal(base[n], base[n].to(ao.BF).double())
+        assert 0 < (base[n] - ex[n]).abs().max().item() <= 2.0 ** -5 * ex[n].abs().max().item()
+    assert torch.equal(base["dv"], ao.format_baseline(q, k, v, do, causal)["dv"])
