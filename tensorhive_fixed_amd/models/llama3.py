@@ -230,7 +230,8 @@ class Llama(nn.Module):
     @torch.no_grad()
     def prefill(self, tokens: torch.Tensor, prompt_lens, cache: KVCache) -> torch.Tensor:
         """Run the left-aligned prompts ``tokens [B, S]`` through the training forward (flash attention,
-        RoPE in place on the packed qkv), copy every layer's rotated K and its V into ``cache`` and set
+        RoPE in place on the packed qkv), store every layer's rotated K and its V in ``cache``
+        (``KVCache.fill``: a copy, or the quantization of an FP8 cache) and set
         the cache lengths to ``prompt_lens``.  Returns the final-norm hidden state ``[B, dim]`` at
         position ``prompt_lens[b] - 1``.  Padding after a prompt is masked out of every real position
         by causality; its cache rows are dead by the lengths."""
@@ -252,8 +253,7 @@ class Llama(nn.Module):
             qkv = linear(h, blk.wqkv)
             o = qkv_attention(qkv, B, S, Hq, Hkv, Dh, c.rope_theta)  # rotates q / k of qkv in place
             kv = qkv.view(B, S, Hq + 2 * Hkv, Dh)
-            cache.k(i)[:, :, :S].copy_(kv[:, :, Hq: Hq + Hkv].transpose(1, 2))
-            cache.v(i)[:, :, :S].copy_(kv[:, :, Hq + Hkv:].transpose(1, 2))
+            cache.fill(i, kv[:, :, Hq: Hq + Hkv].transpose(1, 2), kv[:, :, Hq + Hkv:].transpose(1, 2))
             h, x = rmsnorm_add_fork(linear(o, blk.wo), x, blk.ffn_norm, c.norm_eps)
             pending = linear(swiglu(linear(h, blk.w13)), blk.w2)
         cache.set_lens(lens)
@@ -417,7 +417,8 @@ class Llama(nn.Module):
     def generate(self, tokens: torch.Tensor, prompt_lens=None, max_new_tokens: int = 16,
                  temperature: float = 0.0, top_k: int | None = None,
                  generator: torch.Generator | None = None, return_logits: bool = False,
-                 on_step=None, stream_gemm: bool = False, graph: bool = False, fp8: bool = False):
+                 on_step=None, stream_gemm: bool = False, graph: bool = False, fp8: bool = False,
+                 kv_fp8: bool = False):
         """Continue the left-aligned prompts ``tokens [B, S]`` (``prompt_lens`` defaults to ``S`` for all)
         by ``max_new_tokens`` tokens -> ids ``[B, max_new_tokens]`` (and the f32 logits
         ``[B, max_new_tokens, vocab]`` of every step with ``return_logits``).  ``on_step(i)`` is called
@@ -425,7 +426,10 @@ class Llama(nn.Module):
         every ``decode_step``; the prefill is the same either way.  ``graph`` captures the decode step
         once after the prefill (``decode_graph``) and replays it for every further token.  ``fp8`` runs
         the decode steps on FP8 weights (``decode_step(fp8=True)``), quantizing them first if
-        ``quantize_decode_weights()`` has not been called; the prefill stays on the bf16 weights."""
+        ``quantize_decode_weights()`` has not been called; the prefill stays on the bf16 weights.
+        ``kv_fp8`` keeps the KV cache as FP8 codes with one scale per (token, KV head) row
+        (``KVCache(dtype=torch.float8_e4m3fn)``): the prefill quantizes its rows into it and the decode
+        steps append and attend in FP8; it composes with the other three."""
         B, S = tokens.shape
         lens = [S] * B if prompt_lens is None else [int(n) for n in prompt_lens]
         if max_new_tokens < 1:
@@ -439,7 +443,8 @@ class Llama(nn.Module):
             if self.fp8_weights is None:
                 self.quantize_decode_weights()
             self._need_fp8(B)  # before the prefill, not after it
-        cache = KVCache(self.cfg, B, max_len, tokens.device)
+        cache = KVCache(self.cfg, B, max_len, tokens.device,
+                        dtype=torch.float8_e4m3fn if kv_fp8 else torch.bfloat16)
         if len(lens) != B or min(lens) < 1 or S > tokens.shape[1]:
             raise ValueError(f"generate: prompt lengths {lens} do not fit tokens of shape {tuple(tokens.shape)}")
         live = torch.arange(S, device=tokens.device)[None, :] < torch.tensor(lens, device=tokens.device)[:, None]

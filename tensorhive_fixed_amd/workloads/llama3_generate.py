@@ -5,13 +5,16 @@ Launched like the training payload, one process on one GPU (``python -m
 tensorhive_fixed_amd.workloads.llama3_generate``), typically as a task of the tensorhive job queue.
 It prints ``[th-gen] step=N tokens/s=X batch=B`` lines and ends with one JSON line
 ``{"event": "done", "new_tokens": ..., "prefill_ms": ..., "decode_ms_per_token": ..., "stream_gemm": ...,
-"graph": ..., "fp8_weights": ..., "quantize_ms": ...}``.
+"graph": ..., "fp8_weights": ..., "quantize_ms": ..., "kv_dtype": ..., "kv_cache_mb": ...}``.
 ``--stream-gemm`` runs the decode steps' GEMMs on the weight-streaming kernel of ``ops/decode_linear.py``;
 ``--graph`` captures the decode step once and replays it for every token (``models/decode_graph.py``;
 the capture happens right after the prefill and is counted in ``prefill_ms``).  The two compose.
 ``--fp8-weights`` quantizes the decode-step weights to FP8 after the checkpoint load (``quantize_ms``, not
 counted in ``prefill_ms``) and runs every decode-step GEMM on them (``ops/decode_linear_fp8.py``, batch <= 16);
 it composes with ``--graph`` and takes precedence over ``--stream-gemm``.
+``--fp8-kv`` keeps the KV cache in FP8 (e4m3 codes, one f32 scale per token and KV head:
+``ops/decode_attention.py``), 51.6 % of the bf16 cache's bytes (``kv_cache_mb``); the prefill quantizes its
+rows in torch, which is counted in ``prefill_ms``.  It composes with the other three flags.
 
 The project has no tokenizer: prompts are token ids, from ``--prompt-ids FILE`` (a JSON list of id
 lists, which may be ragged) or synthetic ones drawn like the training data.
@@ -26,6 +29,7 @@ import time
 import torch
 
 from ..models.llama3 import Llama, LlamaConfig
+from ..ops.decode_attention import kv_cache_bytes
 from ..parallel.flat import FlatParamStore
 
 
@@ -90,6 +94,9 @@ def main(argv: list[str] | None = None) -> int:
     ap.add_argument("--fp8-weights", action="store_true",
                     help="decode steps run on FP8 (e4m3, per-row scale) copies of the weights "
                          "(ops/decode_linear_fp8.py); the prefill stays on bf16")
+    ap.add_argument("--fp8-kv", action="store_true",
+                    help="keep the KV cache as FP8 (e4m3) codes with one scale per (token, KV head) row "
+                         "(ops/decode_attention.py, csrc/decode_attn_fp8.hip)")
     args = ap.parse_args(argv)
     from ..utils.blas_env import refuse_unsafe_blas_workspace
 
@@ -127,15 +134,18 @@ def main(argv: list[str] | None = None) -> int:
 
     ids = model.generate(tokens, lens, max_new_tokens=args.max_new_tokens, temperature=args.temperature,
                          top_k=args.top_k, generator=sampler, on_step=on_step, stream_gemm=args.stream_gemm,
-                         graph=args.graph, fp8=args.fp8_weights)
+                         graph=args.graph, fp8=args.fp8_weights, kv_fp8=args.fp8_kv)
     end = sync()
     decode_steps = args.max_new_tokens - 1
+    kv_dtype = torch.float8_e4m3fn if args.fp8_kv else torch.bfloat16
+    kv_bytes = kv_cache_bytes(cfg, batch, max(lens) + args.max_new_tokens, kv_dtype)  # the cache generate() builds
     print(json.dumps({"event": "done", "new_tokens": int(ids.numel()),
                       "prefill_ms": round(1000.0 * (marks["prefill"] - marks["t0"]), 3),
                       "decode_ms_per_token": round(1000.0 * (end - marks["prefill"]) / decode_steps, 3)
                       if decode_steps else None, "stream_gemm": bool(args.stream_gemm),
                       "graph": bool(args.graph), "fp8_weights": bool(args.fp8_weights),
-                      "quantize_ms": quantize_ms}), flush=True)
+                      "quantize_ms": quantize_ms, "kv_dtype": str(kv_dtype).replace("torch.", ""),
+                      "kv_cache_mb": round(kv_bytes / 2 ** 20, 1)}), flush=True)
     return 0
 
 
