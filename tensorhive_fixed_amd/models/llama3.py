@@ -33,6 +33,7 @@ from ..ops.decode_linear import decode_gate_up_swiglu, decode_linear
 from ..ops.decode_linear import preferred as dl_preferred
 from ..ops.decode_linear_fp8 import decode_gate_up_swiglu_fp8, decode_linear_fp8, quantize_weight_fp8, supported_fp8
 from ..ops.embedding import embedding
+from ..ops.extend_attention import extend_attention, rope_append_block
 from ..ops.linear import linear
 from ..ops.mlp import gate_up_swiglu
 from ..ops.rmsnorm import rmsnorm, rmsnorm_add_fork, rmsnorm_fork
@@ -393,6 +394,65 @@ class Llama(nn.Module):
         return decode_linear_fp8(h, *fw["lm_head"], out_dtype=torch.float32)
 
     @torch.no_grad()
+    def extend_step(self, tokens: torch.Tensor, cache: KVCache, stream_gemm: bool = False,
+                    fp8: bool = False) -> torch.Tensor:
+        """``T`` new tokens per sequence at once (``tokens [B, T]``, ``1 <= T <= 8``) on top of a bf16
+        ``cache`` -> f32 logits ``[B, T, vocab]``; advances the cache lengths by ``T``.  It is the body of
+        ``decode_step`` on ``B * T`` rows with ``rope_append_block`` / ``extend_attention``
+        (``ops/extend_attention.py``) in place of the single-token ops: row ``(b, t)`` sits at position
+        ``lens[b] + t`` and attends to the old rows and to the block up to itself.  ``stream_gemm`` dispatches
+        on ``preferred(B * T, ...)``, so more than 16 rows take hipBLASLt; ``fp8`` raises above 16 rows."""
+        self._need_add_norm("extend_step")
+        c = self.cfg
+        if tokens.dim() != 2 or tokens.shape[0] != cache.batch:
+            raise ValueError(f"extend_step: expected token ids [{cache.batch}, T], got shape {tuple(tokens.shape)}")
+        B, T = tokens.shape
+        M = B * T
+        fw = None
+        if fp8:
+            if self.fp8_weights is None:
+                raise ValueError("extend_step(fp8=True): call quantize_decode_weights() first")
+            if M > 16:
+                raise ValueError(f"extend_step(fp8=True): {B} x {T} rows are above the 16 rows of the FP8 decode "
+                                 "kernel (there is no other FP8 path to take)")
+            fw = self.fp8_weights
+
+        def proj(a, w, qw):
+            if fw is not None:
+                return decode_linear_fp8(a, *qw)
+            if stream_gemm and dl_preferred(M, w.shape[0], w.shape[1]):
+                return decode_linear(a, w)
+            return linear(a, w)
+
+        x = embedding(tokens, self.tok_emb).view(M, c.dim)
+        pending = None
+        for i, blk in enumerate(self.layers):
+            qw = fw["layers"][i] if fw is not None else dict.fromkeys(("wqkv", "wo", "w13", "w2"))
+            if pending is None:
+                h, x = _norm(x, blk.attn_norm, c.norm_eps)
+            else:
+                h, x = rmsnorm_add_fork(pending, x, blk.attn_norm, c.norm_eps)
+            q = rope_append_block(proj(h, blk.wqkv, qw["wqkv"]).view(B, T, -1), cache, i)
+            o = extend_attention(q, cache, i).view(M, -1)
+            h, x = rmsnorm_add_fork(proj(o, blk.wo, qw["wo"]), x, blk.ffn_norm, c.norm_eps)
+            if fw is not None:
+                a = decode_gate_up_swiglu_fp8(h, *qw["w13"])
+            elif stream_gemm and dl_preferred(M, c.ffn_dim, c.dim):
+                a = decode_gate_up_swiglu(h, blk.w13)
+            else:
+                a = swiglu(linear(h, blk.w13))
+            pending = proj(a, blk.w2, qw["w2"])
+        cache.advance(T)
+        h = rmsnorm_add_fork(pending, x, self.norm, c.norm_eps)[0]
+        if fw is not None:
+            logits = decode_linear_fp8(h, *fw["lm_head"], out_dtype=torch.float32)
+        elif stream_gemm and dl_preferred(M, c.vocab_size, c.dim):
+            logits = decode_linear(h, self.lm_head, out_dtype=torch.float32)
+        else:
+            logits = torch.mm(h, self.lm_head.t()).float()
+        return logits.view(B, T, -1)
+
+    @torch.no_grad()
     def decode_graph(self, cache: KVCache, stream_gemm: bool = False, fp8: bool = False):
         """``decode_step`` on ``cache`` captured into a graph (``models/decode_graph.py``): the returned
         object's ``step(tokens)`` replays it with one launch per token.  On the CPU it runs the eager step."""
@@ -418,7 +478,7 @@ class Llama(nn.Module):
                  temperature: float = 0.0, top_k: int | None = None,
                  generator: torch.Generator | None = None, return_logits: bool = False,
                  on_step=None, stream_gemm: bool = False, graph: bool = False, fp8: bool = False,
-                 kv_fp8: bool = False):
+                 kv_fp8: bool = False, speculate: int = 0, draft_fn=None, spec_stats: dict | None = None):
         """Continue the left-aligned prompts ``tokens [B, S]`` (``prompt_lens`` defaults to ``S`` for all)
         by ``max_new_tokens`` tokens -> ids ``[B, max_new_tokens]`` (and the f32 logits
         ``[B, max_new_tokens, vocab]`` of every step with ``return_logits``).  ``on_step(i)`` is called
@@ -429,7 +489,16 @@ class Llama(nn.Module):
         ``quantize_decode_weights()`` has not been called; the prefill stays on the bf16 weights.
         ``kv_fp8`` keeps the KV cache as FP8 codes with one scale per (token, KV head) row
         (``KVCache(dtype=torch.float8_e4m3fn)``): the prefill quantizes its rows into it and the decode
-        steps append and attend in FP8; it composes with the other three."""
+        steps append and attend in FP8; it composes with the other three.
+        ``speculate = k`` (1..7) turns on speculative greedy decoding (``_generate_speculative``): every
+        step verifies ``k`` drafted tokens per sequence in one ``extend_step``; the ids are those of the
+        plain greedy run.  It needs ``temperature == 0``, ``graph=False`` and ``kv_fp8=False``.  ``draft_fn``
+        replaces the prompt-lookup drafter and ``spec_stats`` receives the step counts."""
+        if speculate:
+            return self._generate_speculative(tokens, prompt_lens, max_new_tokens, int(speculate), draft_fn,
+                                              spec_stats, temperature=temperature, graph=graph, kv_fp8=kv_fp8,
+                                              return_logits=return_logits, on_step=on_step,
+                                              stream_gemm=stream_gemm, fp8=fp8)
         B, S = tokens.shape
         lens = [S] * B if prompt_lens is None else [int(n) for n in prompt_lens]
         if max_new_tokens < 1:
@@ -465,3 +534,91 @@ class Llama(nn.Module):
                 on_step(i)
         ids = torch.stack(out, dim=1)
         return (ids, torch.stack(steps, dim=1)) if return_logits else ids
+
+    def _generate_speculative(self, tokens, prompt_lens, max_new_tokens, k, draft_fn, spec_stats, *,
+                              temperature, graph, kv_fp8, return_logits, on_step, stream_gemm, fp8):
+        """``generate(speculate=k)``.  After the prefill has chosen token 0, every step feeds
+        ``[last emitted token, k drafts]`` of every sequence to ``extend_step`` (T = k + 1).  Draft ``i`` is
+        accepted while it equals the argmax of the logits row before it; the argmax at the first mismatch
+        (after the last draft, if all match) is emitted as well, so a sequence emits 1..k+1 tokens per step,
+        never more than it still needs.  ``set_lens`` then moves every cache length by what its sequence
+        emitted, which leaves the rejected rows dead.  The ids go to the host once per step (one sync):
+        the acceptance and the drafter (``draft_fn(histories, k) -> k ids per sequence``, default
+        ``speculate.prompt_lookup_draft`` over prompt + emitted ids) run there.  ``on_step(0)`` follows the
+        prefill and ``on_step(n)`` the n-th verification step.  ``spec_stats`` receives ``steps``,
+        ``drafted``, ``accepted`` (drafts that were emitted), per-sequence ``emitted`` and ``cache_lens``."""
+        from .speculate import prompt_lookup_draft
+
+        if not 1 <= k <= 7:
+            raise ValueError(f"generate: speculate must be in [1, 7] (a block holds at most 8 tokens), got {k}")
+        if temperature != 0:
+            raise ValueError("generate: speculate verifies greedy tokens only, it needs temperature == 0")
+        if graph:
+            raise ValueError("generate: speculate does not run on a captured step (graph=True)")
+        if kv_fp8:
+            raise ValueError("generate: speculate needs a bf16 KV cache (kv_fp8=True): block steps have no FP8 kernel")
+        if max_new_tokens < 1:
+            raise ValueError("generate: max_new_tokens must be at least 1")
+        B, S = tokens.shape
+        lens = [S] * B if prompt_lens is None else [int(n) for n in prompt_lens]
+        S = max(lens) if lens else S
+        max_len = S + max_new_tokens + k  # the last step of a sequence may append k rows it does not keep
+        if max_len > self.cfg.max_seq_len:
+            raise ValueError(f"generate: {S} prompt + {max_new_tokens} new + {k} draft tokens exceed max_seq_len "
+                             f"{self.cfg.max_seq_len}")
+        if len(lens) != B or min(lens) < 1 or S > tokens.shape[1]:
+            raise ValueError(f"generate: prompt lengths {lens} do not fit tokens of shape {tuple(tokens.shape)}")
+        if fp8:
+            if self.fp8_weights is None:
+                self.quantize_decode_weights()
+            if B * (k + 1) > 16:
+                raise ValueError(f"generate: fp8 with speculate={k} makes {B} x {k + 1} rows per step, above the "
+                                 "16 rows of the FP8 decode kernel")
+        draft = draft_fn if draft_fn is not None else prompt_lookup_draft
+        cache = KVCache(self.cfg, B, max_len, tokens.device)
+        live = torch.arange(S, device=tokens.device)[None, :] < torch.tensor(lens, device=tokens.device)[:, None]
+        h = self.prefill(tokens[:, :S] * live, lens, cache)
+        logits = torch.mm(h, self.lm_head.t()).float()
+        first = logits.argmax(-1).tolist()
+        hist = [row[:n] + [t] for row, n, t in zip(tokens.tolist(), lens, first)]  # prompt + emitted
+        emitted = [1] * B
+        rows = [[logits[b]] for b in range(B)] if return_logits else None
+        if on_step is not None:
+            on_step(0)
+        stats = {"steps": 0, "drafted": 0, "accepted": 0}
+        while min(emitted) < max_new_tokens:
+            drafts = [[int(t) for t in d] for d in draft([list(x) for x in hist], k)]
+            if len(drafts) != B or any(len(d) != k for d in drafts):
+                raise ValueError(f"generate: draft_fn must return {k} ids for each of the {B} sequences")
+            block = torch.tensor([[x[-1]] + d for x, d in zip(hist, drafts)], dtype=tokens.dtype,
+                                 device=tokens.device)
+            before = list(cache.lens)
+            logits = self.extend_step(block, cache, stream_gemm=stream_gemm, fp8=fp8)
+            pred = logits.argmax(-1).tolist()  # the step's one sync
+            after = []
+            for b in range(B):
+                need = max_new_tokens - emitted[b]
+                if need == 0:  # a finished sequence rides along: its length stays, its rows are dead
+                    after.append(before[b])
+                    continue
+                match = 0
+                while match < k and drafts[b][match] == pred[b][match]:
+                    match += 1
+                a = min(match + 1, need)
+                hist[b] += pred[b][:a]
+                emitted[b] += a
+                after.append(before[b] + a)
+                stats["drafted"] += k
+                stats["accepted"] += min(match, a)
+                if rows is not None:
+                    rows[b] += list(logits[b, :a])
+            cache.set_lens(after)
+            stats["steps"] += 1
+            if on_step is not None:
+                on_step(stats["steps"])
+        if spec_stats is not None:
+            spec_stats.update(stats, emitted=list(emitted), cache_lens=list(cache.lens))
+        ids = torch.tensor([x[n:] for x, n in zip(hist, lens)], dtype=torch.long, device=tokens.device)
+        if return_logits:
+            return ids, torch.stack([torch.stack(r) for r in rows])
+        return ids

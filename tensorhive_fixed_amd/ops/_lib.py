@@ -56,6 +56,8 @@ _SIGS: dict[str, list] = {
     "th_decode_rope_append_fp8": [P, P, P, P, P, P, P, P, P, I, I, I, I, I, L, L, L, L, P],
     "th_decode_attn_fp8": [P, P, P, P, P, P, P, P, I, I, I, I, I, L, L, L, L, I, I, I, F, P],
     "th_decode_attn_fp8_dev": [P, P, P, P, P, P, P, P, I, I, I, I, I, L, L, L, L, I, I, I, I, F, P],
+    "th_decode_rope_append_block": [P, P, P, P, P, P, P, I, I, I, I, I, I, L, L, P],
+    "th_extend_attn": [P, P, P, P, P, P, I, I, I, I, I, I, L, L, I, I, F, P],
     "th_decode_linear": [P, P, P, I, L, I, I, I, P],
     "th_decode_linear_fp8": [P, P, P, P, I, L, I, I, I, P],
 }

@@ -15,6 +15,12 @@ it composes with ``--graph`` and takes precedence over ``--stream-gemm``.
 ``--fp8-kv`` keeps the KV cache in FP8 (e4m3 codes, one f32 scale per token and KV head:
 ``ops/decode_attention.py``), 51.6 % of the bf16 cache's bytes (``kv_cache_mb``); the prefill quantizes its
 rows in torch, which is counted in ``prefill_ms``.  It composes with the other three flags.
+``--speculate K`` (1..7, greedy only, not with ``--graph`` or ``--fp8-kv``) verifies K drafted tokens per
+sequence in every step (``Llama.generate(speculate=K)``, ``ops/extend_attention.py``) and adds ``spec_steps``,
+``tokens_per_step`` (mean tokens a sequence emits per step) and ``ms_per_step`` to the JSON line.  The drafter is
+prompt lookup over the sequence's own ids; ``--drafter oracle`` / ``wrong`` are for measurements: they draft from
+the ids of a plain run made first (not timed), all right (the upper bound) or all wrong (the overhead).
+``--repeat-prompt N`` makes the synthetic prompts repeat an N-token pattern, which prompt lookup can use.
 
 The project has no tokenizer: prompts are token ids, from ``--prompt-ids FILE`` (a JSON list of id
 lists, which may be ragged) or synthetic ones drawn like the training data.
@@ -70,8 +76,25 @@ def _prompts(args, cfg: LlamaConfig, device: torch.device) -> tuple[torch.Tensor
         return tokens.to(device), lens
     gen = torch.Generator(device=device)
     gen.manual_seed(args.seed)
-    tokens = torch.randint(0, cfg.vocab_size, (args.batch, args.prompt_len), device=device, generator=gen)
+    if args.repeat_prompt:
+        pattern = torch.randint(0, cfg.vocab_size, (args.batch, args.repeat_prompt), device=device, generator=gen)
+        tokens = pattern.repeat(1, -(-args.prompt_len // args.repeat_prompt))[:, : args.prompt_len].contiguous()
+    else:
+        tokens = torch.randint(0, cfg.vocab_size, (args.batch, args.prompt_len), device=device, generator=gen)
     return tokens, [args.prompt_len] * args.batch
+
+
+def _reference_drafter(ids: list[list[int]], lens: list[int], vocab: int, right: bool):
+    """A measurement ``draft_fn`` from the ids of a plain run: every draft right, or every draft wrong."""
+    def draft(histories, k):
+        out = []
+        for b, h in enumerate(histories):
+            e = len(h) - lens[b]
+            true = (ids[b] + [0] * k)[e: e + k]
+            out.append(true if right else [(t + 1) % vocab for t in true])
+        return out
+
+    return draft
 
 
 def main(argv: list[str] | None = None) -> int:
@@ -97,6 +120,14 @@ def main(argv: list[str] | None = None) -> int:
     ap.add_argument("--fp8-kv", action="store_true",
                     help="keep the KV cache as FP8 (e4m3) codes with one scale per (token, KV head) row "
                          "(ops/decode_attention.py, csrc/decode_attn_fp8.hip)")
+    ap.add_argument("--speculate", type=int, default=0, metavar="K",
+                    help="speculative greedy decoding: verify K (1..7) drafted tokens per sequence and step "
+                         "(ops/extend_attention.py); not with --graph, --fp8-kv or a temperature")
+    ap.add_argument("--drafter", choices=("lookup", "oracle", "wrong"), default="lookup",
+                    help="lookup: prompt lookup (default); oracle / wrong: drafts from a plain run made first, "
+                         "all right / all wrong (measurements)")
+    ap.add_argument("--repeat-prompt", type=int, default=0, metavar="N",
+                    help="synthetic prompts repeat an N-token pattern")
     args = ap.parse_args(argv)
     from ..utils.blas_env import refuse_unsafe_blas_workspace
 
@@ -126,26 +157,49 @@ def main(argv: list[str] | None = None) -> int:
     def on_step(i: int) -> None:
         if i == 0:
             marks["prefill"] = marks["last"] = sync()
+        elif args.speculate:  # a step emits a varying number of tokens: the rates are printed at the end
+            return
         elif i % args.log_every == 0 or i == args.max_new_tokens - 1:
             now = sync()
             tps = batch * (i - marks["last_step"]) / max(now - marks["last"], 1e-9)
             print(f"[th-gen] step={i} tokens/s={tps:.1f} batch={batch}", flush=True)
             marks["last"], marks["last_step"] = now, i
 
+    spec_stats: dict = {}
+    draft_fn = None
+    if args.speculate:
+        if args.drafter != "lookup":  # the plain run's ids, before any clock starts
+            plain = model.generate(tokens, lens, max_new_tokens=args.max_new_tokens, stream_gemm=args.stream_gemm,
+                                   fp8=args.fp8_weights)
+            draft_fn = _reference_drafter(plain.tolist(), lens, cfg.vocab_size, args.drafter == "oracle")
+            marks["t0"] = sync()
+
     ids = model.generate(tokens, lens, max_new_tokens=args.max_new_tokens, temperature=args.temperature,
                          top_k=args.top_k, generator=sampler, on_step=on_step, stream_gemm=args.stream_gemm,
-                         graph=args.graph, fp8=args.fp8_weights, kv_fp8=args.fp8_kv)
+                         graph=args.graph, fp8=args.fp8_weights, kv_fp8=args.fp8_kv, speculate=args.speculate,
+                         draft_fn=draft_fn, spec_stats=spec_stats)
     end = sync()
+    spec = {}
+    if args.speculate:
+        steps = spec_stats["steps"]
+        per_step = (args.max_new_tokens - 1) / steps if steps else None
+        ms_step = 1000.0 * (end - marks["prefill"]) / steps if steps else None
+        print(f"[th-gen] speculate={args.speculate} drafter={args.drafter} steps={steps} "
+              f"tokens/step={per_step and round(per_step, 3)} ms/step={ms_step and round(ms_step, 3)} "
+              f"accepted={spec_stats['accepted']}/{spec_stats['drafted']}", flush=True)
+        spec = {"speculate": args.speculate, "drafter": args.drafter, "spec_steps": steps,
+                "tokens_per_step": per_step and round(per_step, 3), "ms_per_step": ms_step and round(ms_step, 3),
+                "drafts_accepted": spec_stats["accepted"], "drafts": spec_stats["drafted"]}
     decode_steps = args.max_new_tokens - 1
     kv_dtype = torch.float8_e4m3fn if args.fp8_kv else torch.bfloat16
-    kv_bytes = kv_cache_bytes(cfg, batch, max(lens) + args.max_new_tokens, kv_dtype)  # the cache generate() builds
+    kv_bytes = kv_cache_bytes(cfg, batch, max(lens) + args.max_new_tokens + args.speculate, kv_dtype)  # generate()'s cache
     print(json.dumps({"event": "done", "new_tokens": int(ids.numel()),
                       "prefill_ms": round(1000.0 * (marks["prefill"] - marks["t0"]), 3),
                       "decode_ms_per_token": round(1000.0 * (end - marks["prefill"]) / decode_steps, 3)
                       if decode_steps else None, "stream_gemm": bool(args.stream_gemm),
                       "graph": bool(args.graph), "fp8_weights": bool(args.fp8_weights),
                       "quantize_ms": quantize_ms, "kv_dtype": str(kv_dtype).replace("torch.", ""),
-                      "kv_cache_mb": round(kv_bytes / 2 ** 20, 1)}), flush=True)
+                      "kv_cache_mb": round(kv_bytes / 2 ** 20, 1), **spec}), flush=True)
     return 0
 
 
