@@ -58,11 +58,12 @@ def attention_fp64_fp8(q: torch.Tensor, cache: KVCache, layer: int = 0) -> torch
     rep = Hq // Hkv
     out = torch.zeros(B, Hq, 128, dtype=torch.float64)
     qd = q.detach().cpu().double().view(B, Hkv, rep, 128)
-    kd, vd = dequantized_fp64(cache, layer)
-    for b in range(B):
+    kv, sc = cache.kv[layer].detach().cpu(), cache.kv_scale[layer].detach().cpu()
+    for b in range(B):  # the live rows only, one sequence at a time: a cache may be large
         n = cache.lens[b]
-        s = qd[b] @ kd[b, :, :n].transpose(-1, -2) / math.sqrt(128)
-        out[b] = (s.softmax(-1) @ vd[b, :, :n]).reshape(Hq, 128)
+        kd, vd = (kv[j, b, :, :n].double() * sc[j, b, :, :n].double()[..., None] for j in range(2))
+        s = qd[b] @ kd.transpose(-1, -2) / math.sqrt(128)
+        out[b] = (s.softmax(-1) @ vd).reshape(Hq, 128)
     return out.reshape(B, Hq * 128)
 
 

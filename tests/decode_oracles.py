@@ -7,7 +7,7 @@ from tensorhive_fixed_amd.models.llama3 import LlamaConfig
 from tensorhive_fixed_amd.ops.decode_attention import KVCache
 
 SMAX = 1024
-HEADS = [(2, 2), (4, 1), (8, 2), (8, 1)]  # rep 1, 4, 4, 8
+HEADS = [(2, 2), (4, 2), (4, 1), (8, 2), (8, 1)]  # rep 1, 2, 4, 4, 8
 KV_LENS = [[1], [63, 64, 65], [1, 200, 1024], [257, 256, 255]]
 NSPLITS = [1, 3, 8, None]  # 3 does not divide the lengths, 8 leaves splits empty, None = automatic
 
@@ -76,10 +76,10 @@ def attention_fp64(q: torch.Tensor, cache: KVCache, layer: int = 0) -> torch.Ten
     rep = Hq // Hkv
     out = torch.zeros(B, Hq, 128, dtype=torch.float64)
     qd = q.detach().cpu().double().view(B, Hkv, rep, 128)
-    kv = cache.kv.detach().cpu()
+    kv = cache.kv[layer].detach().cpu()  # one layer: the others may be large
     for b in range(B):
         n = cache.lens[b]
-        k, v = kv[layer, 0, b, :, :n].double(), kv[layer, 1, b, :, :n].double()
+        k, v = kv[0, b, :, :n].double(), kv[1, b, :, :n].double()
         s = qd[b] @ k.transpose(-1, -2) / math.sqrt(128)
         out[b] = (s.softmax(-1) @ v).reshape(Hq, 128)
     return out.reshape(B, Hq * 128)

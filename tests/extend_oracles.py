@@ -7,7 +7,7 @@ from tensorhive_fixed_amd.ops.decode_attention import KVCache
 from tests import decode_oracles as do
 
 SMAX = do.SMAX
-HEADS = do.HEADS + [(2, 1)]  # rep 1, 4, 4, 8 and the tiny config's rep 2
+HEADS = do.HEADS + [(2, 1)]  # rep 1, 2, 4, 4, 8 and the tiny config's rep 2 on one KV head
 BLOCKS = [1, 2, 3, 5, 8]
 # key-tile sizes of csrc/extend_attn.hip: one MFMA tile, a wave's step (two tiles), the workgroup's step
 KEY_TILES = [16, 32, 128]
@@ -43,11 +43,11 @@ def extend_fp64(q: torch.Tensor, cache: KVCache, layer: int = 0) -> torch.Tensor
     rep = Hq // Hkv
     out = torch.zeros(B, T, Hq, 128, dtype=torch.float64)
     qd = q.detach().cpu().double().view(B, T, Hkv, rep, 128)
-    kv = cache.kv.detach().cpu()
+    kv = cache.kv[layer].detach().cpu()  # one layer: the others may be large
     for b in range(B):
         for t in range(T):
             n = cache.lens[b] + t + 1
-            k, v = kv[layer, 0, b, :, :n].double(), kv[layer, 1, b, :, :n].double()
+            k, v = kv[0, b, :, :n].double(), kv[1, b, :, :n].double()
             s = qd[b, t] @ k.transpose(-1, -2) / math.sqrt(128)
             out[b, t] = (s.softmax(-1) @ v).reshape(Hq, 128)
     return out.reshape(B, T, Hq * 128)

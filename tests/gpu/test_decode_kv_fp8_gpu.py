@@ -102,7 +102,7 @@ def _finite_codes():
     return c[(c & 0x7F) != 0x7F]  # 254 of them
 
 
-@pytest.mark.parametrize("rep", [1, 4, 8])
+@pytest.mark.parametrize("rep", [1, 2, 4, 8])
 def test_exact_decode_of_every_code_at_every_byte_position(rep):
     """One live key: p = 1, so o = bf16(code * vscale) exactly, a power-of-two vscale changing nothing.
     Row r of the 256 (sequence, KV head) rows holds code (j + r) mod 254 at byte j: every finite code
@@ -135,7 +135,7 @@ def test_exact_decode_of_every_code_at_every_byte_position(rep):
         assert torch.equal(got, want), (kw, (got != want).nonzero()[:4].tolist())
 
 
-@pytest.mark.parametrize("Hq,Hkv", [(8, 1), (4, 1), (2, 2)])
+@pytest.mark.parametrize("Hq,Hkv", [(8, 1), (4, 1), (4, 2), (2, 2)])
 def test_k_side_index_probe(Hq, Hkv):
     """One-hot q rows (one per dimension over the sequences and heads) against K rows of distinct codes
     and a distinctive V: the score of a key is one K byte, so a byte decoded from the wrong position or a
