@@ -15,6 +15,10 @@
 //     (inside a container, a host pid may be absent or name an unrelated process);
 //   * DRM fdinfo of the amdgpu render nodes (/proc/<pid>/fdinfo/<fd>: drm-pdev, drm-client-id,
 //     drm-memory-vram) -- pids of our own PID namespace, per device BDF, with VRAM.
+//     Where the kernel writes no drm-* keys there (a guest whose KFD has no proc directory and
+//     whose amdsmi lists no process either), the render node's sysfs device link gives the BDF
+//     and /proc/<pid>/maps says whether the process has memory of that node mapped; such a
+//     process is reported with "vram": null.
 // CPU utilisation is a /proc/stat delta between two calls (no `sleep 1`).
 //
 // C ABI (ctypes):  thsmi_init() -> 0 | <0,  thsmi_sample_json(buf, cap) -> bytes | -needed,
@@ -223,6 +227,36 @@ bool has_kfd_open(long pid) {
   return found;
 }
 
+// VRAM of a process that is on a GPU for certain while nothing says with how much ("vram": null)
+constexpr uint64_t kVramUnknown = UINT64_MAX;
+
+// BDF of the PCI device behind /dev/dri/<node>: /sys/class/drm/<node>/device -> ../../../<bdf>
+std::string render_node_bdf(const char* node) {
+  char tgt[256];
+  ssize_t n = readlink((std::string("/sys/class/drm/") + node + "/device").c_str(), tgt, sizeof tgt - 1);
+  if (n <= 0) return "";
+  tgt[n] = 0;
+  const char* s = strrchr(tgt, '/');
+  return s ? s + 1 : tgt;
+}
+
+// the /dev/dri/renderD* nodes a process has mapped (every HIP process opens the render node of
+// every GPU of the node; it maps doorbells and buffers only of those it runs on)
+std::set<std::string> mapped_render_nodes(long pid) {
+  std::set<std::string> out;
+  FILE* f = fopen(("/proc/" + std::to_string(pid) + "/maps").c_str(), "r");
+  if (!f) return out;
+  char line[1024];
+  while (fgets(line, sizeof line, f)) {
+    char* p = strstr(line, "/dev/dri/renderD");
+    if (!p) continue;
+    p[strcspn(p, " \n")] = 0;
+    out.insert(p);
+  }
+  fclose(f);
+  return out;
+}
+
 // DRM fdinfo scan: bdf -> pid -> VRAM bytes (summed over distinct drm clients of the process)
 std::map<std::string, std::map<long, uint64_t>> drm_processes() {
   std::map<std::string, std::map<long, uint64_t>> out;
@@ -236,7 +270,8 @@ std::map<std::string, std::map<long, uint64_t>> drm_processes() {
     const std::string base = std::string("/proc/") + pe->d_name;
     DIR* fd = opendir((base + "/fd").c_str());
     if (!fd) continue;
-    std::set<std::string> clients;
+    std::set<std::string> clients, mapped;
+    bool maps_read = false;
     struct dirent* fe;
     while ((fe = readdir(fd)) != nullptr) {
       if (fe->d_name[0] < '0' || fe->d_name[0] > '9') continue;
@@ -247,7 +282,13 @@ std::map<std::string, std::map<long, uint64_t>> drm_processes() {
       if (strncmp(tgt, "/dev/dri/renderD", 16) != 0) continue;
       std::string info = read_file(base + "/fdinfo/" + fe->d_name, 8192);
       const char* pdev = strstr(info.c_str(), "drm-pdev:");
-      if (!pdev) continue;
+      if (!pdev) {  // no DRM fdinfo from this kernel: the device from sysfs, the use from the maps
+        if (!maps_read) mapped = mapped_render_nodes(pid);
+        maps_read = true;
+        const std::string b = mapped.count(tgt) ? render_node_bdf(tgt + 9) : "";
+        if (!b.empty()) out[b].emplace(pid, kVramUnknown);
+        continue;
+      }
       char bdf[32] = {0};
       sscanf(pdev + 9, " %31s", bdf);
       const char* cid = strstr(info.c_str(), "drm-client-id:");
@@ -261,7 +302,8 @@ std::map<std::string, std::map<long, uint64_t>> drm_processes() {
         sscanf(vm + 16, " %llu %7s", &v, unit);
         vram = v * (unit[0] == 'K' ? 1024ull : unit[0] == 'M' ? 1048576ull : unit[0] == 'G' ? 1073741824ull : 1ull);
       }
-      out[bdf][pid] += vram;
+      uint64_t& sum = out[bdf][pid];
+      sum = (sum == kVramUnknown ? 0 : sum) + vram;
     }
     closedir(fd);
   }
@@ -434,8 +476,10 @@ std::string gpu_json(Gpu& g, const std::map<uint64_t, std::set<long>>& kfd,
     if (has_kfd_open(p.first)) procs[p.first] = p.second;
   auto dit = drm.find(g.bdf);
   if (dit != drm.end())
-    for (const auto& p : dit->second)
-      if (p.second > 0 || procs.count(p.first)) procs[p.first] = std::max(procs[p.first], p.second);
+    for (const auto& p : dit->second) {
+      if (p.second == kVramUnknown) procs.emplace(p.first, kVramUnknown);  // amdsmi's figure stays
+      else if (p.second > 0 || procs.count(p.first)) procs[p.first] = std::max(procs[p.first], p.second);
+    }
   std::string ps = "[";
   bool first = true;
   for (const auto& p : procs) {
@@ -445,7 +489,8 @@ std::string gpu_json(Gpu& g, const std::map<uint64_t, std::set<long>>& kfd,
     if (!first) ps += ",";
     first = false;
     ps += "{\"pid\":" + std::to_string(p.first) + ",\"command\":\"" + esc(pi.cmd) + "\",\"owner\":\"" +
-          esc(pi.owner) + "\",\"uid\":" + std::to_string(pi.uid) + ",\"vram\":" + std::to_string(p.second) +
+          esc(pi.owner) + "\",\"uid\":" + std::to_string(pi.uid) + ",\"vram\":" +
+          (p.second == kVramUnknown ? "null" : std::to_string(p.second)) +
           ",\"task_id\":" + (pi.task_id.empty() ? "null" : "\"" + esc(pi.task_id) + "\"") +
           ",\"ppid\":" + std::to_string(pi.ppid) + ",\"pgid\":" + std::to_string(pi.pgid) +
           ",\"sid\":" + std::to_string(pi.sid) + ",\"ancestors\":[";

@@ -196,14 +196,12 @@ def test_rccl_bench_both_modes_on_one_gpu():
     assert len(ranked["results"]) == 3 * 3 and all(r["gpus"] == 1 for r in ranked["results"])
 
 
-def test_native_tools_under_tsan_on_the_gpu(tmp_path):
-    """ThreadSanitizer on the GPU-side paths: libthsmi's full amdsmi sample from four threads and
-    the th-counters reader (its sampling loop beside rocprofiler-sdk's threads)."""
+def test_libthsmi_under_tsan_on_the_gpu(tmp_path):
+    """ThreadSanitizer on the GPU-side path of libthsmi: its full amdsmi sample from four threads."""
     from tensorhive_fixed_amd.native.build import _build_one, path_of, tsan_argv, tsan_env
 
-    for name in ("thsmi-stress-tsan", "th-counters-tsan"):
-        _, err = _build_one(name, False)
-        assert err is None, err
+    _, err = _build_one("thsmi-stress-tsan", False)
+    assert err is None, err
     rep = tmp_path / "reports"
     rep.mkdir()
     env = {**os.environ, **tsan_env(str(rep))}
@@ -212,6 +210,47 @@ def test_native_tools_under_tsan_on_the_gpu(tmp_path):
     reports = {p.name: p.read_text()[-6000:] for p in rep.iterdir()}
     assert r.returncode == 0 and '"bad":0' in r.stdout and '"gpus":-1' not in r.stdout, (r.stdout, r.stderr[-2000:],
                                                                                           reports)
+    assert reports == {}, reports
+
+
+# Where the kernel puts a new mapping of a process that has /dev/kfd open.
+KFD_MMAP = r"""
+import ctypes, mmap
+kfd = open("/dev/kfd", "rb+", buffering=0)
+m = mmap.mmap(-1, mmap.PAGESIZE)
+print(ctypes.addressof(ctypes.c_char.from_buffer(m)))
+"""
+
+
+def _tsan_cannot_follow_kfd():
+    """ThreadSanitizer has shadow memory for fixed address ranges only and refuses a mapping
+    anywhere else; what the kernel hands out by itself lies in 0x7a00'0000'0000-0x8000'0000'0000 in
+    every x86-64 layout of it.  Some GPU guests' kernels move every later mapping of a process that
+    opens /dev/kfd below 0x5000'0000'0000, hints ignored, and no process can then bring up the HSA
+    runtime under ThreadSanitizer.  Returns that finding as a reason, or None."""
+    from tensorhive_fixed_amd.native.build import tsan_argv
+
+    r = subprocess.run(tsan_argv(sys.executable, "-c", KFD_MMAP), capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0, r.stderr[-2000:]
+    addr = int(r.stdout.split()[-1])
+    if 0x7a0000000000 <= addr < 0x800000000000:
+        return None
+    return f"with /dev/kfd open the kernel maps at {addr:#x}, outside ThreadSanitizer's address ranges"
+
+
+def test_native_tools_under_tsan_on_the_gpu(tmp_path):
+    """ThreadSanitizer on the th-counters reader (its sampling loop beside rocprofiler-sdk's
+    threads); libthsmi's run is the test of its own above, since it needs no HSA runtime."""
+    from tensorhive_fixed_amd.native.build import _build_one, path_of, tsan_argv, tsan_env
+
+    reason = _tsan_cannot_follow_kfd()
+    if reason:
+        pytest.skip(reason)
+    _, err = _build_one("th-counters-tsan", False)
+    assert err is None, err
+    rep = tmp_path / "reports"
+    rep.mkdir()
+    env = {**os.environ, **tsan_env(str(rep))}
     r = subprocess.run(tsan_argv(str(path_of("th-counters-tsan")), "--count", "2", "--window", "100", "--period", "200"),
                        capture_output=True, text=True, timeout=300, env=env)
     reports = {p.name: p.read_text()[-6000:] for p in rep.iterdir()}
