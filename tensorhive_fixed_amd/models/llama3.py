@@ -27,6 +27,7 @@ import torch
 from torch import nn
 
 from ..ops.attention import qkv_attention
+from ..ops.chunk_attention import chunk_attention, rope_append_chunk
 from ..ops.cross_entropy import linear_cross_entropy
 from ..ops.decode_attention import KVCache, decode_attention, rope_append
 from ..ops.decode_linear import decode_gate_up_swiglu, decode_linear
@@ -262,6 +263,62 @@ class Llama(nn.Module):
         return rmsnorm_add_fork(pending[rows].contiguous(), x[rows].contiguous(), self.norm, c.norm_eps)[0]
 
     @torch.no_grad()
+    def prefill_chunk(self, tokens: torch.Tensor, new_lens, cache: KVCache) -> torch.Tensor:
+        """Continue ``cache`` (any state, the empty one included; bf16 only) by the left-aligned chunk
+        ``tokens [B, T]``, of which the first ``new_lens[b]`` (0..T) tokens of sequence ``b`` are live.  It is
+        the body of ``prefill`` on ``B * T`` rows with ``rope_append_chunk`` / ``chunk_attention``
+        (``ops/chunk_attention.py``) in place of the flash forward and ``cache.fill``: row ``(b, t)`` sits at
+        position ``lens[b] + t`` and attends to the old rows and to the chunk up to itself, so ``T`` bounds the
+        activations whatever the cache holds.  Sets the cache lengths to ``lens + new_lens`` (host and device,
+        so a ``DecodeGraph`` captured on the cache keeps working) and returns the final-norm hidden state
+        ``[B, dim]`` at row ``new_lens[b] - 1``.  A sequence with ``new_lens[b] == 0`` is left untouched and
+        its returned row is meaningless."""
+        self._need_add_norm("prefill_chunk")
+        c = self.cfg
+        if tokens.dim() != 2 or tokens.shape[0] != cache.batch or tokens.shape[1] < 1:
+            raise ValueError(f"prefill_chunk: expected token ids [{cache.batch}, T >= 1], got shape "
+                             f"{tuple(tokens.shape)}")
+        B, T = tokens.shape
+        new = [int(n) for n in new_lens]
+        if len(new) != B or min(new) < 0 or max(new) > T or max(a + n for a, n in zip(cache.lens, new)) > cache.max_len:
+            raise ValueError(f"prefill_chunk: new_lens {new} of a [{B}, {T}] chunk do not fit the cache (lengths "
+                             f"{cache.lens}, max_len {cache.max_len})")
+        new_dev = torch.tensor(new, dtype=torch.int32, device=tokens.device)  # one upload for all layers
+        x = embedding(tokens, self.tok_emb).view(B * T, c.dim)
+        pending = None
+        for i, blk in enumerate(self.layers):
+            if pending is None:
+                h, x = _norm(x, blk.attn_norm, c.norm_eps)
+            else:
+                h, x = rmsnorm_add_fork(pending, x, blk.attn_norm, c.norm_eps)
+            q = rope_append_chunk(linear(h, blk.wqkv).view(B, T, -1), cache, i, new, new_dev)
+            o = chunk_attention(q, cache, i, new, new_dev).view(B * T, -1)
+            h, x = rmsnorm_add_fork(linear(o, blk.wo), x, blk.ffn_norm, c.norm_eps)
+            pending = linear(swiglu(linear(h, blk.w13)), blk.w2)
+        cache.set_lens([a + n for a, n in zip(cache.lens, new)])
+        rows = torch.tensor([b * T + max(n, 1) - 1 for b, n in enumerate(new)], device=tokens.device)
+        return rmsnorm_add_fork(pending[rows].contiguous(), x[rows].contiguous(), self.norm, c.norm_eps)[0]
+
+    def _prefill_prompts(self, tokens: torch.Tensor, lens: list[int], S: int, cache: KVCache,
+                         prefill_chunk: int | None) -> torch.Tensor:
+        """The prompts ``tokens[:, :S]`` into the empty ``cache`` -> last-token hidden states ``[B, dim]``:
+        one ``prefill``, or with ``prefill_chunk = N`` one ``prefill_chunk`` call per N tokens, where chunk
+        ``i`` has ``new_lens[b] = clamp(lens[b] - i * N, 0, N)`` and every sequence keeps the hidden state of
+        the chunk its prompt ends in."""
+        live = torch.arange(S, device=tokens.device)[None, :] < torch.tensor(lens, device=tokens.device)[:, None]
+        prompt = tokens[:, :S] * live
+        if prefill_chunk is None:
+            return self.prefill(prompt, lens, cache)
+        N = int(prefill_chunk)
+        out = None
+        for i in range(-(-S // N)):
+            new = [min(max(n - i * N, 0), N) for n in lens]
+            h = self.prefill_chunk(prompt[:, i * N: (i + 1) * N].contiguous(), new, cache)
+            ends = torch.tensor([i * N < n <= (i + 1) * N for n in lens], device=tokens.device)
+            out = h if out is None else torch.where(ends[:, None], h, out)
+        return out
+
+    @torch.no_grad()
     def decode_step(self, tokens: torch.Tensor, cache: KVCache, stream_gemm: bool = False,
                     fp8: bool = False) -> torch.Tensor:
         """One new token per sequence (``tokens [B]``) on top of ``cache`` -> f32 logits ``[B, vocab]``;
@@ -478,7 +535,8 @@ class Llama(nn.Module):
                  temperature: float = 0.0, top_k: int | None = None,
                  generator: torch.Generator | None = None, return_logits: bool = False,
                  on_step=None, stream_gemm: bool = False, graph: bool = False, fp8: bool = False,
-                 kv_fp8: bool = False, speculate: int = 0, draft_fn=None, spec_stats: dict | None = None):
+                 kv_fp8: bool = False, speculate: int = 0, draft_fn=None, spec_stats: dict | None = None,
+                 prefill_chunk: int | None = None):
         """Continue the left-aligned prompts ``tokens [B, S]`` (``prompt_lens`` defaults to ``S`` for all)
         by ``max_new_tokens`` tokens -> ids ``[B, max_new_tokens]`` (and the f32 logits
         ``[B, max_new_tokens, vocab]`` of every step with ``return_logits``).  ``on_step(i)`` is called
@@ -493,12 +551,21 @@ class Llama(nn.Module):
         ``speculate = k`` (1..7) turns on speculative greedy decoding (``_generate_speculative``): every
         step verifies ``k`` drafted tokens per sequence in one ``extend_step``; the ids are those of the
         plain greedy run.  It needs ``temperature == 0``, ``graph=False`` and ``kv_fp8=False``.  ``draft_fn``
-        replaces the prompt-lookup drafter and ``spec_stats`` receives the step counts."""
+        replaces the prompt-lookup drafter and ``spec_stats`` receives the step counts.
+        ``prefill_chunk = N`` prefills the prompts N tokens at a time through ``prefill_chunk`` (activations
+        bounded by ``B * N`` rows, chunks past a short prompt's end cost it nothing) instead of the one-shot
+        ``prefill``; it needs a bf16 cache (``kv_fp8=False``).  ``None`` keeps the one-shot prefill and its bits."""
+        if prefill_chunk is not None:
+            if int(prefill_chunk) < 1:
+                raise ValueError(f"generate: prefill_chunk must be at least 1, got {prefill_chunk}")
+            if kv_fp8:
+                raise ValueError("generate: prefill_chunk needs a bf16 KV cache (kv_fp8=True): chunk steps have no "
+                                 "FP8 kernel")
         if speculate:
             return self._generate_speculative(tokens, prompt_lens, max_new_tokens, int(speculate), draft_fn,
                                               spec_stats, temperature=temperature, graph=graph, kv_fp8=kv_fp8,
                                               return_logits=return_logits, on_step=on_step,
-                                              stream_gemm=stream_gemm, fp8=fp8)
+                                              stream_gemm=stream_gemm, fp8=fp8, prefill_chunk=prefill_chunk)
         B, S = tokens.shape
         lens = [S] * B if prompt_lens is None else [int(n) for n in prompt_lens]
         if max_new_tokens < 1:
@@ -516,8 +583,7 @@ class Llama(nn.Module):
                         dtype=torch.float8_e4m3fn if kv_fp8 else torch.bfloat16)
         if len(lens) != B or min(lens) < 1 or S > tokens.shape[1]:
             raise ValueError(f"generate: prompt lengths {lens} do not fit tokens of shape {tuple(tokens.shape)}")
-        live = torch.arange(S, device=tokens.device)[None, :] < torch.tensor(lens, device=tokens.device)[:, None]
-        h = self.prefill(tokens[:, :S] * live, lens, cache)  # token 0 after every prompt
+        h = self._prefill_prompts(tokens, lens, S, cache, prefill_chunk)  # token 0 after every prompt
         logits = torch.mm(h, self.lm_head.t()).float()
         captured = (self.decode_graph(cache, stream_gemm=stream_gemm, fp8=fp8)
                     if graph and max_new_tokens > 1 else None)
@@ -536,7 +602,8 @@ class Llama(nn.Module):
         return (ids, torch.stack(steps, dim=1)) if return_logits else ids
 
     def _generate_speculative(self, tokens, prompt_lens, max_new_tokens, k, draft_fn, spec_stats, *,
-                              temperature, graph, kv_fp8, return_logits, on_step, stream_gemm, fp8):
+                              temperature, graph, kv_fp8, return_logits, on_step, stream_gemm, fp8,
+                              prefill_chunk=None):
         """``generate(speculate=k)``.  After the prefill has chosen token 0, every step feeds
         ``[last emitted token, k drafts]`` of every sequence to ``extend_step`` (T = k + 1).  Draft ``i`` is
         accepted while it equals the argmax of the logits row before it; the argmax at the first mismatch
@@ -576,8 +643,7 @@ class Llama(nn.Module):
                                  "16 rows of the FP8 decode kernel")
         draft = draft_fn if draft_fn is not None else prompt_lookup_draft
         cache = KVCache(self.cfg, B, max_len, tokens.device)
-        live = torch.arange(S, device=tokens.device)[None, :] < torch.tensor(lens, device=tokens.device)[:, None]
-        h = self.prefill(tokens[:, :S] * live, lens, cache)
+        h = self._prefill_prompts(tokens, lens, S, cache, prefill_chunk)
         logits = torch.mm(h, self.lm_head.t()).float()
         first = logits.argmax(-1).tolist()
         hist = [row[:n] + [t] for row, n, t in zip(tokens.tolist(), lens, first)]  # prompt + emitted

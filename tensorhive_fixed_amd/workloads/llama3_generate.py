@@ -20,6 +20,9 @@ sequence in every step (``Llama.generate(speculate=K)``, ``ops/extend_attention.
 ``tokens_per_step`` (mean tokens a sequence emits per step) and ``ms_per_step`` to the JSON line.  The drafter is
 prompt lookup over the sequence's own ids; ``--drafter oracle`` / ``wrong`` are for measurements: they draft from
 the ids of a plain run made first (not timed), all right (the upper bound) or all wrong (the overhead).
+``--prefill-chunk N`` prefills the prompts N tokens at a time (``Llama.prefill_chunk``, ``ops/chunk_attention.py``):
+the activations are bounded by ``batch * N`` rows and a ragged batch skips the chunks past a short prompt's end; not
+with ``--fp8-kv``.
 ``--repeat-prompt N`` makes the synthetic prompts repeat an N-token pattern, which prompt lookup can use.
 
 The project has no tokenizer: prompts are token ids, from ``--prompt-ids FILE`` (a JSON list of id
@@ -126,6 +129,9 @@ def main(argv: list[str] | None = None) -> int:
     ap.add_argument("--drafter", choices=("lookup", "oracle", "wrong"), default="lookup",
                     help="lookup: prompt lookup (default); oracle / wrong: drafts from a plain run made first, "
                          "all right / all wrong (measurements)")
+    ap.add_argument("--prefill-chunk", type=int, default=None, metavar="N",
+                    help="prefill the prompts N tokens at a time on the chunk attention kernel "
+                         "(ops/chunk_attention.py) instead of in one shot; not with --fp8-kv")
     ap.add_argument("--repeat-prompt", type=int, default=0, metavar="N",
                     help="synthetic prompts repeat an N-token pattern")
     args = ap.parse_args(argv)
@@ -170,14 +176,14 @@ def main(argv: list[str] | None = None) -> int:
     if args.speculate:
         if args.drafter != "lookup":  # the plain run's ids, before any clock starts
             plain = model.generate(tokens, lens, max_new_tokens=args.max_new_tokens, stream_gemm=args.stream_gemm,
-                                   fp8=args.fp8_weights)
+                                   fp8=args.fp8_weights, prefill_chunk=args.prefill_chunk)
             draft_fn = _reference_drafter(plain.tolist(), lens, cfg.vocab_size, args.drafter == "oracle")
             marks["t0"] = sync()
 
     ids = model.generate(tokens, lens, max_new_tokens=args.max_new_tokens, temperature=args.temperature,
                          top_k=args.top_k, generator=sampler, on_step=on_step, stream_gemm=args.stream_gemm,
                          graph=args.graph, fp8=args.fp8_weights, kv_fp8=args.fp8_kv, speculate=args.speculate,
-                         draft_fn=draft_fn, spec_stats=spec_stats)
+                         draft_fn=draft_fn, spec_stats=spec_stats, prefill_chunk=args.prefill_chunk)
     end = sync()
     spec = {}
     if args.speculate:
@@ -199,7 +205,8 @@ def main(argv: list[str] | None = None) -> int:
                       if decode_steps else None, "stream_gemm": bool(args.stream_gemm),
                       "graph": bool(args.graph), "fp8_weights": bool(args.fp8_weights),
                       "quantize_ms": quantize_ms, "kv_dtype": str(kv_dtype).replace("torch.", ""),
-                      "kv_cache_mb": round(kv_bytes / 2 ** 20, 1), **spec}), flush=True)
+                      "kv_cache_mb": round(kv_bytes / 2 ** 20, 1), "prefill_chunk": args.prefill_chunk,
+                      **spec}), flush=True)
     return 0
 
 
