@@ -3,6 +3,7 @@
 a build without it does for the same job.
 
     python scripts/bench_prefill_chunk.py [--parts attn,e2e,gen] [--batches 1,8] [--runs 5] [--out FILE]
+                                          [--min-keys N]
 
 The method is that of ``scripts/bench_decode_speculate.py``: the parent never touches the GPU, every shape is
 a child process under its own time limit, the first child that fails ends the script, and in a child the arms
@@ -11,7 +12,10 @@ alternate (window 0 warms up, ``--runs`` windows each are kept).  One JSON line 
 * ``attn``: 32/8 heads; one ``chunk_attention`` call of T tokens on ``old`` cache rows (``chunk``) against the
   T / 8 ``extend_attention`` calls of 8 tokens that cover the same rows (``extend8``, the lengths advanced on
   the device between them as ``extend_step`` does) and, at ``old = 0``, against the flash forward at S = T
-  (``flash``).  Device events around ``--iters`` rounds; the calls rotate over cache layers.
+  (``flash``).  Where ``pick_chunk_nsplit`` splits the call over the keys (``nsplit`` > 1) a fourth arm,
+  ``chunk_nsplit1``, forces the unsplit kernel, and ``split_wins`` says whether every ``chunk`` window lies
+  below every one of its windows; ``--min-keys`` overrides ``MIN_KEYS_PER_CHUNK_SPLIT`` for a sweep of the
+  rule.  Device events around ``--iters`` rounds; the calls rotate over cache layers.
 * ``e2e``: Llama-3-8B shapes, random weights, B 8: ``prefill_chunk`` of 512 tokens on a 3584-row cache
   (``continue``) against ``prefill`` of all 4096 (``reprefill``); ``continue_wins``: the slowest ``continue``
   window is below the fastest ``reprefill`` window.
@@ -29,7 +33,7 @@ import time
 from pathlib import Path
 
 ROOT = Path(__file__).resolve().parent.parent
-SHAPES = ((512, 3584), (1024, 0), (1024, 3072), (1024, 7168))  # (chunk, old rows)
+SHAPES = ((512, 3584), (1024, 0), (1024, 3072), (1024, 7168), (64, 8192), (128, 8192))  # (chunk, old rows)
 
 
 def _stats(xs: list[float], nd: int = 3) -> dict:
@@ -42,12 +46,16 @@ def child_attn(args) -> int:
 
     from tensorhive_fixed_amd.models.llama3 import LlamaConfig
     from tensorhive_fixed_amd.ops.attention import flash_fwd
+    from tensorhive_fixed_amd.ops import chunk_attention as ca
     from tensorhive_fixed_amd.ops.chunk_attention import chunk_attention
     from tensorhive_fixed_amd.ops.decode_attention import KVCache
     from tensorhive_fixed_amd.ops.extend_attention import extend_attention
 
     dev = torch.device("cuda")
-    Hq, Hkv, B, smax = 32, 8, args.child_batch, 8192
+    Hq, Hkv, B, smax = 32, 8, args.child_batch, max(T + old for T, old in SHAPES)
+    if args.min_keys:
+        ca.MIN_KEYS_PER_CHUNK_SPLIT = args.min_keys
+    cus = torch.cuda.get_device_properties(dev).multi_processor_count
     L = max(4, min(32, (1 << 30) // (2 * B * Hkv * smax * 256)))  # about 1 GiB of K/V under the rotation
     cache = KVCache(LlamaConfig(dim=Hq * 128, n_layers=L, n_heads=Hq, n_kv_heads=Hkv, max_seq_len=smax), B, smax, dev)
     cache.kv.normal_()
@@ -77,7 +85,14 @@ def child_attn(args) -> int:
             cache.set_lens([old] * B)
             chunk_attention(q, cache, i % L, new, new_dev)
 
+        def chunk_nsplit1(i):
+            cache.set_lens([old] * B)
+            chunk_attention(q, cache, i % L, new, new_dev, nsplit=1)
+
+        nsplit = ca.pick_chunk_nsplit(B, Hkv, Hq // Hkv, T, old + T, cus)
         arms = {"chunk": chunk, "extend8": extend8}
+        if nsplit > 1:  # otherwise `chunk` is the unsplit kernel itself
+            arms["chunk_nsplit1"] = chunk_nsplit1
         if old == 0:
             qkv = torch.randn(B * T, (Hq + 2 * Hkv) * 128, device=dev, dtype=torch.bfloat16)
             arms["flash"] = lambda i: flash_fwd(qkv, B, T, Hq, Hkv, 128)
@@ -89,7 +104,11 @@ def child_attn(args) -> int:
                 if r:
                     t[k].append(x)
         res = {"bench": "attn", "batch": B, "heads": [Hq, Hkv], "chunk": T, "old_rows": old, "layers_rotated": L,
-               "runs": args.runs, "iters": args.iters, **{k + "_ms": _stats(v) for k, v in t.items()}}
+               "runs": args.runs, "iters": args.iters, "nsplit": nsplit,
+               "min_keys_per_split": ca.MIN_KEYS_PER_CHUNK_SPLIT, **{k + "_ms": _stats(v) for k, v in t.items()}}
+        if nsplit > 1:
+            res["ratio_to_nsplit1"] = round(res["chunk_ms"]["median"] / res["chunk_nsplit1_ms"]["median"], 3)
+            res["split_wins"] = max(t["chunk"]) < min(t["chunk_nsplit1"])
         pairs = B * Hq * (T * old + T * (T + 1) // 2)
         res["chunk_tflops"] = round(4 * 128 * pairs / res["chunk_ms"]["median"] / 1e9, 1)
         res["ratio_to_extend8"] = round(res["chunk_ms"]["median"] / res["extend8_ms"]["median"], 3)
@@ -175,6 +194,7 @@ def main() -> int:
     ap.add_argument("--iters", type=int, default=20, help="attention rounds per window")
     ap.add_argument("--attn-timeout", type=int, default=240, help="seconds per attention child")
     ap.add_argument("--model-timeout", type=int, default=300, help="seconds per model child")
+    ap.add_argument("--min-keys", type=int, default=0, help="override MIN_KEYS_PER_CHUNK_SPLIT (attention part)")
     ap.add_argument("--out", default=None, help="append the JSON lines to this file too")
     ap.add_argument("--child", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--child-batch", type=int, default=0, help=argparse.SUPPRESS)
@@ -189,7 +209,8 @@ def main() -> int:
         return {"attn": child_attn, "e2e": child_e2e, "gen": child_gen}[args.child](args)
 
     def run(extra: list[str], limit: int) -> bool:
-        cmd = [sys.executable, str(Path(__file__).resolve()), "--runs", str(args.runs), "--iters", str(args.iters)] + extra
+        cmd = [sys.executable, str(Path(__file__).resolve()), "--runs", str(args.runs), "--iters", str(args.iters),
+               "--min-keys", str(args.min_keys)] + extra
         try:
             r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=limit)
         except subprocess.TimeoutExpired:

@@ -14,11 +14,16 @@ the cache's device, so that a model step uploads it once and not once per layer.
 The kernels are in ``csrc/chunk_attn.hip``: a workgroup serves ``QUERY_TILE`` query rows of one KV head
 (``QUERY_TILE / rep`` consecutive tokens times the ``rep`` query heads), its four waves share K / V tiles
 of ``KEY_TILE`` keys through LDS, and no partial leaves the workgroup, so two runs give the same bits.
-Out of scope here:
+
+A short chunk on a long cache has too few query tiles to fill the device, so ``chunk_attention`` then
+splits every tile's own causal key range into ``nsplit`` equal parts of whole key tiles
+(``th_chunk_attn_split``): ``nsplit`` times as many workgroups write unnormalised f32 partials into
+``cache.workspace`` and a second kernel merges them in split order, with no atomic, so two runs still
+give the same bits (they differ from the unsplit kernel's by the f32 rounding of the merge).
+``pick_chunk_nsplit`` is the rule; ``nsplit=`` overrides it (tests, benchmarks).  Out of scope here:
 
 * an FP8 cache (a ``ValueError``: chunk steps need a bf16 cache);
-* a split over the keys for short chunks on long caches: for ``T <= 8`` ``extend_attention`` remains the
-  right call, and nothing dispatches between the two;
+* for ``T <= 8`` ``extend_attention`` remains the right call, and nothing dispatches between the two;
 * isolation from a NaN in a *live* later row of the same chunk (``0 * NaN`` in the PV product).  Rows at
   or past ``lens[b] + new_lens[b]`` are never read and may hold anything.
 
@@ -37,6 +42,22 @@ from .rope import rope_tables
 
 QUERY_TILE = 128  # query rows (token x query head of one KV head) of a workgroup
 KEY_TILE = 64     # keys per staged K / V tile
+MAX_CHUNK_SPLITS = 16
+# fewest keys of the longest sequence per split.  At or below 1024 keys a call is never split.  Measured
+# (profiles/prefill_chunk_split): B 1, 32 / 8 heads, 64 or 128 tokens on 8192 rows take 0.074 ms at 1024
+# (8 splits), 0.095 ms at 2048 (4) and 0.150 ms at 4096 (2) against 0.26 ms unsplit; 512 tokens on 3584
+# rows take 0.092 ms at 1024 or 2048 (2 splits) against 0.143 ms at 4096 (unsplit).  1024 stays.
+MIN_KEYS_PER_CHUNK_SPLIT = 1024
+WS_FLOATS_PER_ROW = HEAD_DIM + 2  # a partial: the row's f32 accumulators and (m, l)
+
+
+def pick_chunk_nsplit(batch: int, n_kv_heads: int, rep: int, T: int, longest_keys: int, n_cus: int) -> int:
+    """Smallest split count that gives every CU a workgroup (``qtiles * n_kv_heads * batch * nsplit >=
+    n_cus``), never leaving the longest sequence fewer than ``MIN_KEYS_PER_CHUNK_SPLIT`` keys per split
+    nor exceeding ``MAX_CHUNK_SPLITS``.  ``longest_keys`` is ``max(lens[b] + new_lens[b])``."""
+    qtiles = -(-T * rep // QUERY_TILE)
+    want = -(-n_cus // (qtiles * n_kv_heads * batch))
+    return max(1, min(want, longest_keys // MIN_KEYS_PER_CHUNK_SPLIT, MAX_CHUNK_SPLITS))
 
 
 def _check_chunk(x: torch.Tensor, cache: KVCache, cols: int, layer: int, new_lens, new_dev, what: str):
@@ -128,15 +149,30 @@ def chunk_attention_reference(q: torch.Tensor, cache: KVCache, layer: int, new_l
 
 
 def chunk_attention(q: torch.Tensor, cache: KVCache, layer: int, new_lens,
-                    new_dev: torch.Tensor | None = None) -> torch.Tensor:
+                    new_dev: torch.Tensor | None = None, nsplit: int | None = None) -> torch.Tensor:
     """``q [B, T, Hq*128]`` (the output of ``rope_append_chunk``) against ``layer`` -> ``o`` of the same
-    shape; module docstring."""
+    shape; module docstring.  ``nsplit`` overrides ``pick_chunk_nsplit`` (1: the unsplit kernel); CPU
+    tensors ignore it."""
     Hq, Hkv = cache.n_heads, cache.n_kv_heads
     T, new, new_dev = _check_chunk(q, cache, Hq * HEAD_DIM, layer, new_lens, new_dev, "chunk_attention")
+    if nsplit is not None and not 1 <= int(nsplit) <= MAX_CHUNK_SPLITS:
+        raise ValueError(f"chunk_attention: nsplit must be in [1, {MAX_CHUNK_SPLITS}], got {nsplit}")
     if not q.is_cuda:
         return chunk_attention_reference(q, cache, layer, new)
+    rep = Hq // Hkv
+    if nsplit is None:
+        cus = torch.cuda.get_device_properties(q.device).multi_processor_count
+        nsplit = pick_chunk_nsplit(cache.batch, Hkv, rep, T, max(a + n for a, n in zip(cache.lens, new)), cus)
+    nsplit = int(nsplit)
     o = torch.empty_like(q)
     kc, vc = cache.k(layer), cache.v(layer)
+    if nsplit > 1:
+        qtiles = -(-T * rep // QUERY_TILE)
+        ws = cache.workspace(cache.batch * Hkv * qtiles * nsplit * QUERY_TILE * WS_FLOATS_PER_ROW)
+        _lib.call("th_chunk_attn_split", q.data_ptr(), kc.data_ptr(), vc.data_ptr(), cache.lens_dev.data_ptr(),
+                  new_dev.data_ptr(), o.data_ptr(), ws.data_ptr(), cache.batch, T, Hq, Hkv, HEAD_DIM, cache.max_len,
+                  kc.stride(0), kc.stride(1), nsplit, 1.0 / math.sqrt(HEAD_DIM), _lib.stream_ptr(q.device))
+        return o
     _lib.call("th_chunk_attn", q.data_ptr(), kc.data_ptr(), vc.data_ptr(), cache.lens_dev.data_ptr(),
               new_dev.data_ptr(), o.data_ptr(), cache.batch, T, Hq, Hkv, HEAD_DIM, cache.max_len, kc.stride(0),
               kc.stride(1), 1.0 / math.sqrt(HEAD_DIM), _lib.stream_ptr(q.device))

@@ -3,8 +3,11 @@
 //
 // Cache of one layer as in decode_attn.hip: K and V as [B, Hkv, Smax, 128] bf16, the entry points
 // take the layer's K / V base pointers and the b / head strides in elements.  Head dim 128 only.
+// th-build-flags: -fno-slp-vectorize -Xclang -target-feature -Xclang -packed-fp32-ops
+//   (no v_pk_*_f32 in the f32 softmax math beside the MFMAs; the host pass ignores the feature.  The build
+//   reads this line from the file's first 40 lines only: it stays up here)
 //
-// th_chunk_rope_append   row (b, t < new_len[b]) of qkv [B, T, (Hq+2*Hkv)*128] is rotated at
+// th_chunk_rope_append  row (b, t < new_len[b]) of qkv [B, T, (Hq+2*Hkv)*128] is rotated at
 //                        kv_len[b] + t; its k / v go into cache row kv_len[b] + t and its q into
 //                        q_out [B, T, Hq*128], with the arithmetic of th_decode_rope_append.  A row
 //                        t >= new_len[b] writes nothing to the cache and zeros to q_out.
@@ -37,8 +40,27 @@
 //   row and written as zeros; cache rows at or past kv_len[b] + new_len[b] are never loaded.  A tile
 //   with no live row writes zeros and reads no K / V.  kv_len and new_len are clamped on the device
 //   (kv_len + new_len <= Smax) before any address is formed.
-// th-build-flags: -fno-slp-vectorize -Xclang -target-feature -Xclang -packed-fp32-ops
-//   (no v_pk_*_f32 in the f32 softmax math beside the MFMAs; the host pass ignores the feature)
+//
+// th_chunk_attn_split    the same rows for a short chunk on a long cache, where (query tile, Hkv, B) leaves
+//                        most CUs idle: chunk_attn_kernel<true> on a grid (nsplit x query tile, Hkv, B) and
+//                        chunk_attn_combine_kernel.  chunk_attn_kernel<false> is the kernel described above,
+//                        with its argument block and its instructions.
+//   A workgroup (tile, split s) derives kv_end and ntiles of its tile as above and serves the key tiles
+//   [s * tps, min((s + 1) * tps, ntiles)), tps = ceil(ntiles / nsplit): every tile of every sequence is cut
+//   into equal parts of its own causal range, in whole key tiles, so the loop, its masks and its wave skip
+//   are the unsplit ones and only nsplit depends on the lengths.  A partial is unnormalised f32 in a
+//   workspace slot of WS_SLOT floats per (b, hkv, tile, split): 128 x (m, l) (m scaled, base 2, uniform
+//   over the lane pair; l pair-summed), then per wave its 32 x 128 accumulators in register order, piece
+//   (d, g) = acc[d][4 g .. 4 g + 3] of lane L at float 4 * ((4 d + g) * 64 + L): a store instruction of a
+//   wave covers 1024 contiguous bytes and nothing passes through LDS.  A workgroup with no key tile (or a
+//   tile with no live row) writes (-inf, 0) and returns before any K / V or Q load; a wave that computed
+//   no tile writes its (m, l) = (-inf, 0) only.
+//   The combine workgroup serves the 32 rows of one wave block: thread (wave d, lane L) reads the pieces
+//   (d, 0..3) of lane L of every split, whole 1024-byte runs per wave as they were written, skips every
+//   partial with l == 0 without reading its accumulators (the workspace is not cleared), weights the
+//   others by exp2(m_s - max m) in split order, swaps halves with lane L ^ 32 (which holds the other 4 of
+//   every 8 dims of the same row) and writes 2 x 16 bytes of bf16; rows t >= new_len[b] and rows with no
+//   key are exact zeros.  No atomic and no counter: two runs give the same bits.
 #include "th_common.h"
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -53,6 +75,9 @@ constexpr int DH = 128;
 constexpr int QTILE = 128;         // query rows of a workgroup: 4 waves x 32
 constexpr int KTILE = 64;          // keys per staged tile
 constexpr int IMG = KTILE * DH * 2;  // bytes of one K or V image
+constexpr int MAX_CHUNK_SPLITS = 16;
+constexpr int WS_ML = 2 * QTILE;                 // floats of a slot's (m, l) pairs
+constexpr int WS_SLOT = WS_ML + QTILE * DH;      // floats of one (b, hkv, tile, split) partial
 
 // byte offset of (row, 16-byte chunk) in an image: 8-row x 32-column subtiles of 512 B, the slot of a
 // chunk inside its 64 B is xor-ed with (row >> 2) & 3 (flash_attn.hip's img_off)
@@ -129,12 +154,31 @@ __device__ __forceinline__ void chunk_lens(const int* kv_len, const int* new_len
   nw = n > Smax - l ? Smax - l : n;
 }
 
+__device__ __forceinline__ float* split_ws(float* ws, int) { return ws; }
+__device__ __forceinline__ int split_count(float*, int nsplit) { return nsplit; }
+
+// a row's (m, l) = (-inf, 0): the neutral partial, which the combine pass skips
+__device__ __forceinline__ void store_neutral(float* slot, int w, int c32, int h) {
+  if (h == 0) *reinterpret_cast<float2*>(slot + 2 * (w * 32 + c32)) = make_float2(-INFINITY, 0.f);
+}
+
+// SPLIT: `sp...` is (float* ws, int nsplit) and `o` is not written; otherwise there is no `sp` and the
+// argument block is that of the unsplit kernel
+template <bool SPLIT, typename... SP>
 __global__ __launch_bounds__(256, 2) void chunk_attn_kernel(
     const ushort* __restrict__ q, const ushort* __restrict__ kc, const ushort* __restrict__ vc,
     const int* __restrict__ kv_len, const int* __restrict__ new_len, ushort* __restrict__ o, int T, int Hq,
-    int Smax, long stride_b, long stride_h, int rep_shift, float qscale) {
+    int Smax, long stride_b, long stride_h, int rep_shift, float qscale, SP... sp) {
   __shared__ __attribute__((aligned(16))) char smem[2 * 2 * IMG];  // (K, V) x 2 buffers
-  const int qt = gridDim.x - 1 - blockIdx.x, hkv = blockIdx.y, b = blockIdx.z;  // furthest tile first
+  int nsplit = 1, split = 0, xt = blockIdx.x, qtiles = gridDim.x;
+  float* slot = nullptr;
+  if constexpr (SPLIT) {
+    nsplit = split_count(sp...);
+    xt = blockIdx.x / nsplit;
+    split = blockIdx.x - xt * nsplit;
+    qtiles = gridDim.x / nsplit;
+  }
+  const int qt = qtiles - 1 - xt, hkv = blockIdx.y, b = blockIdx.z;  // furthest tile first
   const int tid = threadIdx.x, lane = tid & 63, h = lane >> 5, c32 = lane & 31;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int rep = 1 << rep_shift;
@@ -151,14 +195,29 @@ __global__ __launch_bounds__(256, 2) void chunk_attn_kernel(
 #pragma unroll
   for (int d = 0; d < 4; ++d) acc[d] = f32x16(0.f);
 
+  if constexpr (SPLIT)
+    slot = split_ws(sp...) + ((((long)b * gridDim.y + hkv) * qtiles + qt) * nsplit + split) * WS_SLOT;
   if (tok0 >= nw) {  // no live row: zeros, no K / V read
-    if (t < T) store_row(orow, acc, 0.f, false, h);
+    if constexpr (SPLIT)
+      store_neutral(slot, w, c32, h);
+    else if (t < T)
+      store_row(orow, acc, 0.f, false, h);
     return;
   }
 
   const int tl = min(tok0 + (QTILE >> rep_shift), nw) - 1;  // last live token of the tile
   const int kv_end = len0 + tl + 1;                         // keys the tile's last live row sees (>= 1)
   const int ntiles = (kv_end + KTILE - 1) / KTILE;
+  int j0 = 0, j1 = ntiles;  // this workgroup's key tiles
+  if constexpr (SPLIT) {
+    const int tps = (ntiles + nsplit - 1) / nsplit;
+    j0 = split * tps;
+    j1 = min(j0 + tps, ntiles);
+    if (j0 >= j1) {  // fewer key tiles than splits: nothing to read
+      store_neutral(slot, w, c32, h);
+      return;
+    }
+  }
   const int tc = t < nw ? t : nw - 1;  // dead rows are loaded from the last live one
   const int lim = len0 + tc + 1;       // this row sees keys < lim
   // wave-uniform: the wave's first and last live token
@@ -197,17 +256,17 @@ __global__ __launch_bounds__(256, 2) void chunk_attn_kernel(
     }
   };
 
-  load_tile(0);
-  store_tile(0);
-  if (ntiles > 1) load_tile(1);
+  load_tile(j0);
+  store_tile(j0 & 1);
+  if (j0 + 1 < j1) load_tile(j0 + 1);
   __syncthreads();
 
   float m_i = -INFINITY, l_i = 0.f;  // l_i: this lane's 32 keys per tile; the pair is summed at the end
-  for (int j = 0; j < ntiles; ++j) {
+  for (int j = j0; j < j1; ++j) {
     // the other image was last read in iteration j - 1, which ended with a barrier
-    if (j + 1 < ntiles) {
+    if (j + 1 < j1) {
       store_tile((j + 1) & 1);
-      if (j + 2 < ntiles) load_tile(j + 2);
+      if (j + 2 < j1) load_tile(j + 2);
     }
     const int kbase = j * KTILE;
     if (wave_live && kbase < wlast) {  // wave-uniform
@@ -258,9 +317,81 @@ __global__ __launch_bounds__(256, 2) void chunk_attn_kernel(
     __syncthreads();
   }
 
-  if (t < T) {
+  if constexpr (SPLIT) {
+    const float l = pair_sum(l_i);
+    if (h == 0) *reinterpret_cast<float2*>(slot + 2 * (w * 32 + c32)) = make_float2(m_i, l);
+    if (wave_live && j0 * KTILE < wlast) {  // wave-uniform: the wave computed a tile
+      float* ap = slot + WS_ML + w * (32 * DH) + 4 * lane;
+#pragma unroll
+      for (int d = 0; d < 4; ++d)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          const float4v v = {acc[d][4 * g], acc[d][4 * g + 1], acc[d][4 * g + 2], acc[d][4 * g + 3]};
+          *reinterpret_cast<float4v*>(ap + (4 * d + g) * 256) = v;
+        }
+    }
+  } else if (t < T) {
     const float l = pair_sum(l_i);
     store_row(orow, acc, l > 0.f ? 1.f / l : 0.f, t < nw, h);
+  }
+}
+
+// lanes 0..31 get {x, x of lane + 32}, lanes 32..63 get {y of lane - 32, y}
+__device__ __forceinline__ void pair_swap(float x, float y, float& lo, float& hi) {
+  const auto r = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(int, x), __builtin_bit_cast(int, y), false, false);
+  lo = __builtin_bit_cast(float, (int)r[0]);
+  hi = __builtin_bit_cast(float, (int)r[1]);
+}
+
+// grid (4 x query tile, Hkv, B): the 32 rows of wave block blockIdx.x & 3; header comment
+__global__ __launch_bounds__(256) void chunk_attn_combine_kernel(
+    const float* __restrict__ ws, const int* __restrict__ kv_len, const int* __restrict__ new_len,
+    ushort* __restrict__ o, int T, int Hq, int Smax, int rep_shift, int nsplit) {
+  const int qt = blockIdx.x >> 2, wb = blockIdx.x & 3, hkv = blockIdx.y, b = blockIdx.z;
+  const int qtiles = gridDim.x >> 2;
+  const int tid = threadIdx.x, lane = tid & 63, h = lane >> 5, d = tid >> 6;
+  const int rep = 1 << rep_shift;
+  int len0, nw;
+  chunk_lens(kv_len, new_len, b, T, Smax, len0, nw);
+  const int r = qt * QTILE + wb * 32 + (lane & 31);  // both lanes of a pair serve this row
+  const int t = r >> rep_shift, hh = r & (rep - 1);
+  if (t >= T) return;
+  const float* slot = ws + (((long)b * gridDim.y + hkv) * qtiles + qt) * nsplit * WS_SLOT;
+  const float* ml = slot + 2 * (wb * 32 + (lane & 31));
+  const float* ap = slot + WS_ML + wb * (32 * DH) + (4 * d) * 256 + 4 * lane;
+
+  float4v a[4] = {float4v(0.f), float4v(0.f), float4v(0.f), float4v(0.f)};
+  float L = 0.f;
+  if (t < nw) {
+    float M = -INFINITY;
+    for (int s = 0; s < nsplit; ++s) {
+      const float2 x = *reinterpret_cast<const float2*>(ml + (long)s * WS_SLOT);
+      if (x.y != 0.f) M = fmaxf(M, x.x);
+    }
+    for (int s = 0; s < nsplit; ++s) {
+      const float2 x = *reinterpret_cast<const float2*>(ml + (long)s * WS_SLOT);
+      if (x.y == 0.f) continue;  // a neutral partial: its accumulators were never written
+      const float wgt = fexp2(x.x - M);
+      L += wgt * x.y;
+#pragma unroll
+      for (int g = 0; g < 4; ++g) a[g] += wgt * *reinterpret_cast<const float4v*>(ap + (long)s * WS_SLOT + g * 256);
+    }
+  }
+  const bool live = L > 0.f;  // false for t >= nw and for a row that saw no key (never NaN: L is then 0)
+  const float f = live ? 1.f / L : 0.f;
+  // a[g] holds dims 32 d + 8 g + 4 h + 0..3 of the row; after the swap this lane has 32 d + 16 h + 0..15
+  ushort* orow = o + (((long)b * T + t) * Hq + hkv * rep + hh) * DH + 32 * d + 16 * h;
+#pragma unroll
+  for (int x = 0; x < 2; ++x) {
+    ushort8 v;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      float lo, hi;
+      pair_swap(a[x][e], a[2 + x][e], lo, hi);
+      v[e] = live ? f2bf(lo * f) : (ushort)0;
+      v[4 + e] = live ? f2bf(hi * f) : (ushort)0;
+    }
+    *reinterpret_cast<ushort8*>(orow + 8 * x) = v;
   }
 }
 
@@ -345,7 +476,28 @@ extern "C" int th_chunk_attn(const void* q, const void* kcache, const void* vcac
   const int rep_shift = rep == 1 ? 0 : rep == 2 ? 1 : rep == 4 ? 2 : 3;
   const dim3 grid((T * rep + QTILE - 1) / QTILE, Hkv, B);
   const float qscale = scale * 1.4426950408889634f;  // scores in the base-2 domain
-  chunk_attn_kernel<<<grid, 256, 0, s>>>((const ushort*)q, (const ushort*)kcache, (const ushort*)vcache, kv_len,
+  chunk_attn_kernel<false><<<grid, 256, 0, s>>>((const ushort*)q, (const ushort*)kcache, (const ushort*)vcache, kv_len,
                                          new_len, (ushort*)o, T, Hq, Smax, stride_b, stride_h, rep_shift, qscale);
+  TH_CHECK_LAUNCH();
+}
+
+// th_chunk_attn on a grid of nsplit x as many workgroups; ws: B * Hkv * ceil(T * rep / 128) * nsplit * 128 * 130
+// floats, which need not be cleared.
+extern "C" int th_chunk_attn_split(const void* q, const void* kcache, const void* vcache, const int* kv_len,
+                                   const int* new_len, void* o, void* ws, int B, int T, int Hq, int Hkv, int Dh,
+                                   int Smax, long stride_b, long stride_h, int nsplit, float scale, hipStream_t s) {
+  if (!chunk_geometry_ok(B, T, Hq, Hkv, Dh, Smax, stride_b, stride_h) || nsplit < 2 || nsplit > MAX_CHUNK_SPLITS)
+    return -1;
+  const int rep = Hq / Hkv;
+  const int rep_shift = rep == 1 ? 0 : rep == 2 ? 1 : rep == 4 ? 2 : 3;
+  const int qtiles = (int)(((long)T * rep + QTILE - 1) / QTILE);
+  const float qscale = scale * 1.4426950408889634f;  // scores in the base-2 domain
+  chunk_attn_kernel<true><<<dim3(qtiles * nsplit, Hkv, B), 256, 0, s>>>(
+      (const ushort*)q, (const ushort*)kcache, (const ushort*)vcache, kv_len, new_len, (ushort*)o, T, Hq, Smax,
+      stride_b, stride_h, rep_shift, qscale, (float*)ws, nsplit);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return (int)e;
+  chunk_attn_combine_kernel<<<dim3(qtiles * 4, Hkv, B), 256, 0, s>>>((const float*)ws, kv_len, new_len, (ushort*)o,
+                                                                     T, Hq, Smax, rep_shift, nsplit);
   TH_CHECK_LAUNCH();
 }
