@@ -229,6 +229,12 @@ class Llama(nn.Module):
             raise RuntimeError(f"Llama.{what} runs the fused add+norm flow only: unset TH_ADD_NORM=0 / "
                                "TH_RMSNORM_FORK=0")
 
+    @staticmethod
+    def _refuse_paged(cache, what: str) -> None:
+        if getattr(cache, "is_paged", False):
+            raise ValueError(f"Llama.{what}: a paged KV cache (PagedKVCache) runs prefill and decode_step only; "
+                             f"{what} has no paged kernel")
+
     @torch.no_grad()
     def prefill(self, tokens: torch.Tensor, prompt_lens, cache: KVCache) -> torch.Tensor:
         """Run the left-aligned prompts ``tokens [B, S]`` through the training forward (flash attention,
@@ -245,6 +251,9 @@ class Llama(nn.Module):
             raise ValueError(f"prefill: prompts {lens} in a [{B}, {S}] batch do not fit the cache "
                              f"(batch {cache.batch}, max_len {cache.max_len})")
         Hq, Hkv, Dh = c.n_heads, c.n_kv_heads, c.head_dim
+        if getattr(cache, "is_paged", False):  # pages for the prompts, before anything is computed
+            for b, n in enumerate(lens):
+                cache.reserve(b, n)
         x = embedding(tokens, self.tok_emb).view(B * S, c.dim)
         pending = None
         for i, blk in enumerate(self.layers):
@@ -274,6 +283,7 @@ class Llama(nn.Module):
         ``[B, dim]`` at row ``new_lens[b] - 1``.  A sequence with ``new_lens[b] == 0`` is left untouched and
         its returned row is meaningless."""
         self._need_add_norm("prefill_chunk")
+        self._refuse_paged(cache, "prefill_chunk")
         c = self.cfg
         if tokens.dim() != 2 or tokens.shape[0] != cache.batch or tokens.shape[1] < 1:
             raise ValueError(f"prefill_chunk: expected token ids [{cache.batch}, T >= 1], got shape "
@@ -460,6 +470,7 @@ class Llama(nn.Module):
         ``lens[b] + t`` and attends to the old rows and to the block up to itself.  ``stream_gemm`` dispatches
         on ``preferred(B * T, ...)``, so more than 16 rows take hipBLASLt; ``fp8`` raises above 16 rows."""
         self._need_add_norm("extend_step")
+        self._refuse_paged(cache, "extend_step")
         c = self.cfg
         if tokens.dim() != 2 or tokens.shape[0] != cache.batch:
             raise ValueError(f"extend_step: expected token ids [{cache.batch}, T], got shape {tuple(tokens.shape)}")
@@ -515,6 +526,7 @@ class Llama(nn.Module):
         object's ``step(tokens)`` replays it with one launch per token.  On the CPU it runs the eager step."""
         from .decode_graph import DecodeGraph
 
+        self._refuse_paged(cache, "decode_graph")
         return DecodeGraph(self, cache, stream_gemm=stream_gemm, fp8=fp8)
 
     @staticmethod
@@ -536,7 +548,7 @@ class Llama(nn.Module):
                  generator: torch.Generator | None = None, return_logits: bool = False,
                  on_step=None, stream_gemm: bool = False, graph: bool = False, fp8: bool = False,
                  kv_fp8: bool = False, speculate: int = 0, draft_fn=None, spec_stats: dict | None = None,
-                 prefill_chunk: int | None = None):
+                 prefill_chunk: int | None = None, paged_kv: bool = False):
         """Continue the left-aligned prompts ``tokens [B, S]`` (``prompt_lens`` defaults to ``S`` for all)
         by ``max_new_tokens`` tokens -> ids ``[B, max_new_tokens]`` (and the f32 logits
         ``[B, max_new_tokens, vocab]`` of every step with ``return_logits``).  ``on_step(i)`` is called
@@ -554,7 +566,17 @@ class Llama(nn.Module):
         replaces the prompt-lookup drafter and ``spec_stats`` receives the step counts.
         ``prefill_chunk = N`` prefills the prompts N tokens at a time through ``prefill_chunk`` (activations
         bounded by ``B * N`` rows, chunks past a short prompt's end cost it nothing) instead of the one-shot
-        ``prefill``; it needs a bf16 cache (``kv_fp8=False``).  ``None`` keeps the one-shot prefill and its bits."""
+        ``prefill``; it needs a bf16 cache (``kv_fp8=False``).  ``None`` keeps the one-shot prefill and its bits.
+        ``paged_kv`` keeps the rows in a ``PagedKVCache`` (``ops/paged_attention.py``) of
+        ``sum_b ceil((lens[b] + max_new_tokens) / 64)`` pages, every sequence's pages reserved before the
+        prefill, instead of ``B * (max(lens) + max_new_tokens)`` rows; it runs the plain loop and refuses
+        ``graph``, ``kv_fp8``, ``speculate`` and ``prefill_chunk``."""
+        if paged_kv:
+            for name, on in (("graph", graph), ("kv_fp8", kv_fp8), ("speculate", speculate),
+                             ("prefill_chunk", prefill_chunk is not None)):
+                if on:
+                    raise ValueError(f"generate: paged_kv does not combine with {name}: a paged KV cache runs "
+                                     "prefill and plain decode steps only")
         if prefill_chunk is not None:
             if int(prefill_chunk) < 1:
                 raise ValueError(f"generate: prefill_chunk must be at least 1, got {prefill_chunk}")
@@ -579,10 +601,18 @@ class Llama(nn.Module):
             if self.fp8_weights is None:
                 self.quantize_decode_weights()
             self._need_fp8(B)  # before the prefill, not after it
-        cache = KVCache(self.cfg, B, max_len, tokens.device,
-                        dtype=torch.float8_e4m3fn if kv_fp8 else torch.bfloat16)
         if len(lens) != B or min(lens) < 1 or S > tokens.shape[1]:
             raise ValueError(f"generate: prompt lengths {lens} do not fit tokens of shape {tuple(tokens.shape)}")
+        if paged_kv:
+            from ..ops.paged_attention import PagedKVCache, pages_for
+
+            cache = PagedKVCache(self.cfg, B, max_len, sum(pages_for(n + max_new_tokens) for n in lens),
+                                 tokens.device)
+            for b, n in enumerate(lens):  # up front: the table does not change during decode
+                cache.reserve(b, n + max_new_tokens)
+        else:
+            cache = KVCache(self.cfg, B, max_len, tokens.device,
+                            dtype=torch.float8_e4m3fn if kv_fp8 else torch.bfloat16)
         h = self._prefill_prompts(tokens, lens, S, cache, prefill_chunk)  # token 0 after every prompt
         logits = torch.mm(h, self.lm_head.t()).float()
         captured = (self.decode_graph(cache, stream_gemm=stream_gemm, fp8=fp8)

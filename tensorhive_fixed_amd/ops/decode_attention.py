@@ -24,6 +24,9 @@ and ``decode_attention`` dispatch on ``cache.kv.dtype``; on an FP8 cache the app
 k row to bf16 and quantizes it (v as it comes), and the attention is over ``codes * scale``
 (``csrc/decode_attn_fp8.hip``).  67,584 bytes per token against 131,072 for Llama-3-8B.
 
+Paged cache (opt-in): ``rope_append`` and ``decode_attention`` forward a ``PagedKVCache`` (``is_paged``) to
+``ops/paged_attention.py``, whose kernels follow a per-sequence page table (``csrc/paged_attn.hip``).
+
 GPU tensors run the gfx950 kernels (a missing entry point raises, there is no SDPA fallback);
 CPU tensors run the fp32 reference below, which is also the tests' oracle.
 """
@@ -203,6 +206,10 @@ def rope_append_reference(qkv: torch.Tensor, cache: KVCache, layer: int) -> torc
 def rope_append(qkv: torch.Tensor, cache: KVCache, layer: int) -> torch.Tensor:
     """Rotate q / k of the new token rows ``qkv [B, (Hq+2*Hkv)*128]`` at ``lens[b]``, store k / v in
     cache row ``lens[b]`` of ``layer`` and return the rotated q ``[B, Hq*128]``."""
+    if getattr(cache, "is_paged", False):  # a PagedKVCache: its own kernels (ops/paged_attention.py)
+        from .paged_attention import paged_rope_append
+
+        return paged_rope_append(qkv, cache, layer)
     Hq, Hkv = cache.n_heads, cache.n_kv_heads
     _check(qkv, cache, (Hq + 2 * Hkv) * HEAD_DIM, layer, 1, "rope_append")
     if not qkv.is_cuda:
@@ -270,6 +277,12 @@ def decode_attention(q: torch.Tensor, cache: KVCache, layer: int, nsplit: int | 
     and chunk from ``lens_dev`` inside the kernel (``device_split_geometry``) under a grid of
     ``pick_nsplit`` at ``max_len`` splits, or of ``nsplit`` where given; nothing the launch is given then
     depends on the current lengths, and the output has the bits of the host rule."""
+    if getattr(cache, "is_paged", False):
+        from .paged_attention import paged_decode_attention
+
+        if device_geometry:
+            raise ValueError("decode_attention: a paged KV cache has no device_geometry form (no captured steps)")
+        return paged_decode_attention(q, cache, layer, nsplit=nsplit, new=new)
     Hq, Hkv = cache.n_heads, cache.n_kv_heads
     _check(q, cache, Hq * HEAD_DIM, layer, new, "decode_attention")
     if nsplit is not None and not 1 <= int(nsplit) <= 1024:

@@ -23,6 +23,10 @@ the ids of a plain run made first (not timed), all right (the upper bound) or al
 ``--prefill-chunk N`` prefills the prompts N tokens at a time (``Llama.prefill_chunk``, ``ops/chunk_attention.py``):
 the activations are bounded by ``batch * N`` rows and a ragged batch skips the chunks past a short prompt's end; not
 with ``--fp8-kv``.
+``--paged-kv`` keeps the rows in a paged cache (``ops/paged_attention.py``: pages of 64 rows, every sequence holds
+``ceil((prompt + new tokens) / 64)`` of them instead of the longest sequence's rows); ``kv_cache_mb`` is then the
+pool and ``kv_dense_mb`` what the dense cache would have taken.  Not with ``--graph``, ``--fp8-kv``, ``--speculate``
+or ``--prefill-chunk``.
 ``--repeat-prompt N`` makes the synthetic prompts repeat an N-token pattern, which prompt lookup can use.
 
 The project has no tokenizer: prompts are token ids, from ``--prompt-ids FILE`` (a JSON list of id
@@ -132,6 +136,9 @@ def main(argv: list[str] | None = None) -> int:
     ap.add_argument("--prefill-chunk", type=int, default=None, metavar="N",
                     help="prefill the prompts N tokens at a time on the chunk attention kernel "
                          "(ops/chunk_attention.py) instead of in one shot; not with --fp8-kv")
+    ap.add_argument("--paged-kv", action="store_true",
+                    help="keep the KV rows in a paged cache (ops/paged_attention.py, csrc/paged_attn.hip); not with "
+                         "--graph, --fp8-kv, --speculate or --prefill-chunk")
     ap.add_argument("--repeat-prompt", type=int, default=0, metavar="N",
                     help="synthetic prompts repeat an N-token pattern")
     args = ap.parse_args(argv)
@@ -183,7 +190,8 @@ def main(argv: list[str] | None = None) -> int:
     ids = model.generate(tokens, lens, max_new_tokens=args.max_new_tokens, temperature=args.temperature,
                          top_k=args.top_k, generator=sampler, on_step=on_step, stream_gemm=args.stream_gemm,
                          graph=args.graph, fp8=args.fp8_weights, kv_fp8=args.fp8_kv, speculate=args.speculate,
-                         draft_fn=draft_fn, spec_stats=spec_stats, prefill_chunk=args.prefill_chunk)
+                         draft_fn=draft_fn, spec_stats=spec_stats, prefill_chunk=args.prefill_chunk,
+                         paged_kv=args.paged_kv)
     end = sync()
     spec = {}
     if args.speculate:
@@ -199,6 +207,14 @@ def main(argv: list[str] | None = None) -> int:
     decode_steps = args.max_new_tokens - 1
     kv_dtype = torch.float8_e4m3fn if args.fp8_kv else torch.bfloat16
     kv_bytes = kv_cache_bytes(cfg, batch, max(lens) + args.max_new_tokens + args.speculate, kv_dtype)  # generate()'s cache
+    paged = {}
+    if args.paged_kv:
+        from ..ops.paged_attention import paged_cache_bytes, pages_for
+
+        paged = {"paged_kv": True, "kv_dense_mb": round(kv_bytes / 2 ** 20, 1)}
+        kv_bytes = paged_cache_bytes(cfg, sum(pages_for(n + args.max_new_tokens) for n in lens))  # generate()'s pool
+        print(f"[th-gen] paged KV pool {kv_bytes} bytes, the dense cache would take "
+              f"{kv_cache_bytes(cfg, batch, max(lens) + args.max_new_tokens)} bytes", flush=True)
     print(json.dumps({"event": "done", "new_tokens": int(ids.numel()),
                       "prefill_ms": round(1000.0 * (marks["prefill"] - marks["t0"]), 3),
                       "decode_ms_per_token": round(1000.0 * (end - marks["prefill"]) / decode_steps, 3)
@@ -206,7 +222,7 @@ def main(argv: list[str] | None = None) -> int:
                       "graph": bool(args.graph), "fp8_weights": bool(args.fp8_weights),
                       "quantize_ms": quantize_ms, "kv_dtype": str(kv_dtype).replace("torch.", ""),
                       "kv_cache_mb": round(kv_bytes / 2 ** 20, 1), "prefill_chunk": args.prefill_chunk,
-                      **spec}), flush=True)
+                      **spec, **paged}), flush=True)
     return 0
 
 
