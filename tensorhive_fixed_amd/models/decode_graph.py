@@ -28,7 +28,7 @@ from ..ops.decode_attention import KVCache
 class DecodeGraph:
     """``step(tokens [B]) -> logits [B, vocab] f32`` on top of ``cache``; built by ``Llama.decode_graph``."""
 
-    def __init__(self, model, cache: KVCache, stream_gemm: bool = False, fp8: bool = False):
+    def __init__(self, model, cache: KVCache, stream_gemm: bool = False, fp8: bool = False, mxfp4: bool = False):
         model._need_add_norm("decode_graph")
         if cache.cfg != model.cfg:
             raise ValueError("decode_graph: the cache was built for another model configuration")
@@ -38,7 +38,13 @@ class DecodeGraph:
             raise ValueError(f"decode_graph: the cache is full ({max(cache.lens)} of {cache.max_len} rows): "
                              "no dead row to warm up on")
         self.model, self.cache, self.stream_gemm, self.fp8 = model, cache, bool(stream_gemm), bool(fp8)
-        if self.fp8:  # takes precedence, as in decode_step; the FP8 weights must not be re-quantized while it lives
+        self.mxfp4 = bool(mxfp4)
+        if self.mxfp4:  # the step on MXFP4 weights, all GEMMs the project's own kernels as with fp8
+            if self.fp8:
+                raise ValueError("decode_graph: mxfp4 and fp8 name two weight formats, choose one")
+            model._need_mxfp4(cache.batch)
+            self._body = model._decode_step_mxfp4
+        elif self.fp8:  # takes precedence, as in decode_step; the FP8 weights must not be re-quantized while it lives
             model._need_fp8(cache.batch)
             self._body = model._decode_step_fp8
         else:
@@ -80,7 +86,8 @@ class DecodeGraph:
             raise ValueError(f"DecodeGraph.step: {max(cache.lens)} + 1 rows exceed the cache's max_len "
                              f"{cache.max_len}")
         if self._graph is None:
-            return self.model.decode_step(tokens, cache, stream_gemm=self.stream_gemm, fp8=self.fp8)
+            return self.model.decode_step(tokens, cache, stream_gemm=self.stream_gemm, fp8=self.fp8,
+                                          mxfp4=self.mxfp4)
         self._tokens.copy_(tokens)
         self._graph.replay()
         cache.advance_host(1)  # the replay advanced lens_dev

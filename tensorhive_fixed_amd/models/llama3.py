@@ -33,6 +33,8 @@ from ..ops.decode_attention import KVCache, decode_attention, rope_append
 from ..ops.decode_linear import decode_gate_up_swiglu, decode_linear
 from ..ops.decode_linear import preferred as dl_preferred
 from ..ops.decode_linear_fp8 import decode_gate_up_swiglu_fp8, decode_linear_fp8, quantize_weight_fp8, supported_fp8
+from ..ops.decode_linear_mxfp4 import (decode_gate_up_swiglu_mxfp4, decode_linear_mxfp4, quantize_weight_mxfp4,
+                                       supported_mxfp4)
 from ..ops.embedding import embedding
 from ..ops.extend_attention import extend_attention, rope_append_block
 from ..ops.linear import linear
@@ -162,6 +164,8 @@ class Llama(nn.Module):
         # (wq, scale) pairs of the decode-step weights, built by quantize_decode_weights(); a plain
         # attribute holding plain tensors: no Parameter, no buffer, invisible to state_dict()
         self.fp8_weights = None
+        # the same for (codes, scales) pairs, built by quantize_decode_weights_mxfp4()
+        self.mxfp4_weights = None
         self.reset_parameters(seed)
 
     @torch.no_grad()
@@ -330,17 +334,23 @@ class Llama(nn.Module):
 
     @torch.no_grad()
     def decode_step(self, tokens: torch.Tensor, cache: KVCache, stream_gemm: bool = False,
-                    fp8: bool = False) -> torch.Tensor:
+                    fp8: bool = False, mxfp4: bool = False) -> torch.Tensor:
         """One new token per sequence (``tokens [B]``) on top of ``cache`` -> f32 logits ``[B, vocab]``;
         advances the cache lengths by one.  ``stream_gemm`` runs the projections and the LM head on the
         weight-streaming kernel of ``ops/decode_linear.py`` wherever its ``preferred`` allows.  ``fp8``
         (which takes precedence) runs all of them on the FP8 weights of ``quantize_decode_weights()``
-        with ``ops/decode_linear_fp8.py``; it raises when they are missing or the batch is above 16."""
+        with ``ops/decode_linear_fp8.py``; it raises when they are missing or the batch is above 16.
+        ``mxfp4`` does the same on the MXFP4 weights of ``quantize_decode_weights_mxfp4()`` with
+        ``ops/decode_linear_mxfp4.py``; it does not combine with ``fp8``."""
         self._need_add_norm("decode_step")
         c = self.cfg
         B = tokens.shape[0]
         if tokens.dim() != 1 or B != cache.batch:
             raise ValueError(f"decode_step: expected {cache.batch} token ids, got shape {tuple(tokens.shape)}")
+        if mxfp4:
+            if fp8:
+                raise ValueError("decode_step: mxfp4 and fp8 name two weight formats, choose one")
+            return self._decode_step_mxfp4(tokens, cache)
         if fp8:
             return self._decode_step_fp8(tokens, cache)
         if stream_gemm:
@@ -439,9 +449,15 @@ class Llama(nn.Module):
         and SwiGLU in one call, f32 logits from the f32 accumulator.  No shape falls back to the bf16
         weights, so the numerics do not depend on the batch size.  ``device_geometry`` and ``advance``
         as in ``_decode_step_plain``."""
+        return self._decode_step_quantized(tokens, cache, self._need_fp8(tokens.shape[0]), decode_linear_fp8,
+                                           decode_gate_up_swiglu_fp8, device_geometry, advance)
+
+    def _decode_step_quantized(self, tokens: torch.Tensor, cache: KVCache, fw: dict, lin, glu,
+                               device_geometry: bool, advance) -> torch.Tensor:
+        """The step on the quantized weights ``fw`` with ``lin(x, *pair, out_dtype=...)`` for the four
+        projections and the LM head and ``glu(x, *pair)`` for gate|up + SwiGLU."""
         c = self.cfg
         B = tokens.shape[0]
-        fw = self._need_fp8(B)
         x = embedding(tokens.view(B, 1), self.tok_emb).view(B, c.dim)
         pending = None
         for i, (blk, q) in enumerate(zip(self.layers, fw["layers"])):
@@ -449,16 +465,47 @@ class Llama(nn.Module):
                 h, x = _norm(x, blk.attn_norm, c.norm_eps)
             else:
                 h, x = rmsnorm_add_fork(pending, x, blk.attn_norm, c.norm_eps)
-            qv = rope_append(decode_linear_fp8(h, *q["wqkv"]), cache, i)
+            qv = rope_append(lin(h, *q["wqkv"]), cache, i)
             o = decode_attention(qv, cache, i, new=1, device_geometry=device_geometry)
-            h, x = rmsnorm_add_fork(decode_linear_fp8(o, *q["wo"]), x, blk.ffn_norm, c.norm_eps)
-            pending = decode_linear_fp8(decode_gate_up_swiglu_fp8(h, *q["w13"]), *q["w2"])
+            h, x = rmsnorm_add_fork(lin(o, *q["wo"]), x, blk.ffn_norm, c.norm_eps)
+            pending = lin(glu(h, *q["w13"]), *q["w2"])
         if advance is None:
             cache.advance(1)
         else:
             advance()
         h = rmsnorm_add_fork(pending, x, self.norm, c.norm_eps)[0]
-        return decode_linear_fp8(h, *fw["lm_head"], out_dtype=torch.float32)
+        return lin(h, *fw["lm_head"], out_dtype=torch.float32)
+
+    @torch.no_grad()
+    def quantize_decode_weights_mxfp4(self) -> None:
+        """Build and keep the OCP MXFP4 form (``ops/decode_linear_mxfp4.quantize_weight_mxfp4``: two E2M1
+        codes per byte and one E8M0 scale byte per 32 elements along K) of the weights that
+        ``quantize_decode_weights`` covers, for ``decode_step(mxfp4=True)``.  The bf16 parameters stay
+        (the prefill runs on them), so this adds 0.27 of their bytes.  Call it again after the parameters
+        change.  A weight shape the MXFP4 kernel does not take raises here."""
+        ws = [(f"layers.{i}.{n}", getattr(blk, n)) for i, blk in enumerate(self.layers)
+              for n in ("wqkv", "wo", "w13", "w2")] + [("lm_head", self.lm_head)]
+        for name, w in ws:
+            if not supported_mxfp4(1, w.shape[0], w.shape[1]):
+                raise ValueError(f"quantize_decode_weights_mxfp4: {name} {tuple(w.shape)} is outside the MXFP4 "
+                                 "decode kernel's shape rule (ops/decode_linear_mxfp4.supported_mxfp4)")
+        q = {name: quantize_weight_mxfp4(w.detach().contiguous()) for name, w in ws}
+        self.mxfp4_weights = {"layers": [{n: q[f"layers.{i}.{n}"] for n in ("wqkv", "wo", "w13", "w2")}
+                                         for i in range(len(self.layers))], "lm_head": q["lm_head"]}
+
+    def _need_mxfp4(self, B: int) -> dict:
+        if self.mxfp4_weights is None:
+            raise ValueError("decode_step(mxfp4=True): call quantize_decode_weights_mxfp4() first")
+        if B > 16:
+            raise ValueError(f"decode_step(mxfp4=True): batch {B} is above the 16 rows of the MXFP4 decode kernel "
+                             "(there is no other MXFP4 path to take)")
+        return self.mxfp4_weights
+
+    def _decode_step_mxfp4(self, tokens: torch.Tensor, cache: KVCache, device_geometry: bool = False,
+                           advance=None) -> torch.Tensor:
+        """``_decode_step_fp8`` on the MXFP4 weights (``ops/decode_linear_mxfp4.py``)."""
+        return self._decode_step_quantized(tokens, cache, self._need_mxfp4(tokens.shape[0]), decode_linear_mxfp4,
+                                           decode_gate_up_swiglu_mxfp4, device_geometry, advance)
 
     @torch.no_grad()
     def extend_step(self, tokens: torch.Tensor, cache: KVCache, stream_gemm: bool = False,
@@ -521,13 +568,13 @@ class Llama(nn.Module):
         return logits.view(B, T, -1)
 
     @torch.no_grad()
-    def decode_graph(self, cache: KVCache, stream_gemm: bool = False, fp8: bool = False):
+    def decode_graph(self, cache: KVCache, stream_gemm: bool = False, fp8: bool = False, mxfp4: bool = False):
         """``decode_step`` on ``cache`` captured into a graph (``models/decode_graph.py``): the returned
         object's ``step(tokens)`` replays it with one launch per token.  On the CPU it runs the eager step."""
         from .decode_graph import DecodeGraph
 
         self._refuse_paged(cache, "decode_graph")
-        return DecodeGraph(self, cache, stream_gemm=stream_gemm, fp8=fp8)
+        return DecodeGraph(self, cache, stream_gemm=stream_gemm, fp8=fp8, mxfp4=mxfp4)
 
     @staticmethod
     def sample(logits: torch.Tensor, temperature: float = 0.0, top_k: int | None = None,
@@ -548,7 +595,7 @@ class Llama(nn.Module):
                  generator: torch.Generator | None = None, return_logits: bool = False,
                  on_step=None, stream_gemm: bool = False, graph: bool = False, fp8: bool = False,
                  kv_fp8: bool = False, speculate: int = 0, draft_fn=None, spec_stats: dict | None = None,
-                 prefill_chunk: int | None = None, paged_kv: bool = False):
+                 prefill_chunk: int | None = None, paged_kv: bool = False, mxfp4: bool = False):
         """Continue the left-aligned prompts ``tokens [B, S]`` (``prompt_lens`` defaults to ``S`` for all)
         by ``max_new_tokens`` tokens -> ids ``[B, max_new_tokens]`` (and the f32 logits
         ``[B, max_new_tokens, vocab]`` of every step with ``return_logits``).  ``on_step(i)`` is called
@@ -570,7 +617,19 @@ class Llama(nn.Module):
         ``paged_kv`` keeps the rows in a ``PagedKVCache`` (``ops/paged_attention.py``) of
         ``sum_b ceil((lens[b] + max_new_tokens) / 64)`` pages, every sequence's pages reserved before the
         prefill, instead of ``B * (max(lens) + max_new_tokens)`` rows; it runs the plain loop and refuses
-        ``graph``, ``kv_fp8``, ``speculate`` and ``prefill_chunk``."""
+        ``graph``, ``kv_fp8``, ``speculate`` and ``prefill_chunk``.
+        ``mxfp4`` runs the decode steps on MXFP4 weights (``decode_step(mxfp4=True)``), quantizing them first
+        if ``quantize_decode_weights_mxfp4()`` has not been called; it composes with ``stream_gemm`` (ignored),
+        ``graph``, ``kv_fp8`` and ``paged_kv``, which touch only attention, and refuses ``fp8``, ``speculate``
+        (block steps have no MXFP4 path) and batches above 16."""
+        if mxfp4:
+            if fp8:
+                raise ValueError("generate: mxfp4 and fp8 name two weight formats, choose one")
+            if speculate:
+                raise ValueError("generate: mxfp4 does not combine with speculate: block steps have no MXFP4 path")
+            if tokens.shape[0] > 16:
+                raise ValueError(f"generate: mxfp4 with batch {tokens.shape[0]} is above the 16 rows of the MXFP4 "
+                                 "decode kernel")
         if paged_kv:
             for name, on in (("graph", graph), ("kv_fp8", kv_fp8), ("speculate", speculate),
                              ("prefill_chunk", prefill_chunk is not None)):
@@ -601,6 +660,8 @@ class Llama(nn.Module):
             if self.fp8_weights is None:
                 self.quantize_decode_weights()
             self._need_fp8(B)  # before the prefill, not after it
+        if mxfp4 and self.mxfp4_weights is None:
+            self.quantize_decode_weights_mxfp4()
         if len(lens) != B or min(lens) < 1 or S > tokens.shape[1]:
             raise ValueError(f"generate: prompt lengths {lens} do not fit tokens of shape {tuple(tokens.shape)}")
         if paged_kv:
@@ -615,14 +676,14 @@ class Llama(nn.Module):
                             dtype=torch.float8_e4m3fn if kv_fp8 else torch.bfloat16)
         h = self._prefill_prompts(tokens, lens, S, cache, prefill_chunk)  # token 0 after every prompt
         logits = torch.mm(h, self.lm_head.t()).float()
-        captured = (self.decode_graph(cache, stream_gemm=stream_gemm, fp8=fp8)
+        captured = (self.decode_graph(cache, stream_gemm=stream_gemm, fp8=fp8, mxfp4=mxfp4)
                     if graph and max_new_tokens > 1 else None)
         out, steps = [], []
         for i in range(max_new_tokens):
             if i and captured is not None:
                 logits = captured.step(out[-1])
             elif i:
-                logits = self.decode_step(out[-1], cache, stream_gemm=stream_gemm, fp8=fp8)
+                logits = self.decode_step(out[-1], cache, stream_gemm=stream_gemm, fp8=fp8, mxfp4=mxfp4)
             out.append(self.sample(logits, temperature, top_k, generator))
             if return_logits:
                 steps.append(logits.clone() if captured is not None else logits)  # a replay reuses its output

@@ -65,6 +65,7 @@ _SIGS: dict[str, list] = {
     "th_paged_decode_attn": [P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, L, L, I, I, I, F, P],
     "th_decode_linear": [P, P, P, I, L, I, I, I, P],
     "th_decode_linear_fp8": [P, P, P, P, I, L, I, I, I, P],
+    "th_decode_linear_mxfp4": [P, P, P, P, I, L, I, I, I, P],
 }
 
 

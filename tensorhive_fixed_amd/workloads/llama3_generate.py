@@ -12,6 +12,9 @@ the capture happens right after the prefill and is counted in ``prefill_ms``).  
 ``--fp8-weights`` quantizes the decode-step weights to FP8 after the checkpoint load (``quantize_ms``, not
 counted in ``prefill_ms``) and runs every decode-step GEMM on them (``ops/decode_linear_fp8.py``, batch <= 16);
 it composes with ``--graph`` and takes precedence over ``--stream-gemm``.
+``--mxfp4-weights`` does the same with OCP MXFP4 copies (``ops/decode_linear_mxfp4.py``, 0.53 bytes per weight;
+``mxfp4_weights`` in the JSON line); it composes with ``--graph``, ``--fp8-kv`` and ``--paged-kv`` and refuses
+``--fp8-weights``, ``--speculate`` and batches above 16.
 ``--fp8-kv`` keeps the KV cache in FP8 (e4m3 codes, one f32 scale per token and KV head:
 ``ops/decode_attention.py``), 51.6 % of the bf16 cache's bytes (``kv_cache_mb``); the prefill quantizes its
 rows in torch, which is counted in ``prefill_ms``.  It composes with the other three flags.
@@ -124,6 +127,9 @@ def main(argv: list[str] | None = None) -> int:
     ap.add_argument("--fp8-weights", action="store_true",
                     help="decode steps run on FP8 (e4m3, per-row scale) copies of the weights "
                          "(ops/decode_linear_fp8.py); the prefill stays on bf16")
+    ap.add_argument("--mxfp4-weights", action="store_true",
+                    help="decode steps run on OCP MXFP4 (E2M1 codes, one E8M0 scale per 32 elements) copies of the "
+                         "weights (ops/decode_linear_mxfp4.py); batch <= 16, not with --fp8-weights or --speculate")
     ap.add_argument("--fp8-kv", action="store_true",
                     help="keep the KV cache as FP8 (e4m3) codes with one scale per (token, KV head) row "
                          "(ops/decode_attention.py, csrc/decode_attn_fp8.hip)")
@@ -165,6 +171,10 @@ def main(argv: list[str] | None = None) -> int:
         t = sync()
         model.quantize_decode_weights()
         quantize_ms = round(1000.0 * (sync() - t), 3)
+    if args.mxfp4_weights and not args.fp8_weights:  # both: generate refuses below
+        t = sync()
+        model.quantize_decode_weights_mxfp4()
+        quantize_ms = round(1000.0 * (sync() - t), 3)
     marks = {"t0": sync(), "last": None, "last_step": 0}
 
     def on_step(i: int) -> None:
@@ -191,7 +201,7 @@ def main(argv: list[str] | None = None) -> int:
                          top_k=args.top_k, generator=sampler, on_step=on_step, stream_gemm=args.stream_gemm,
                          graph=args.graph, fp8=args.fp8_weights, kv_fp8=args.fp8_kv, speculate=args.speculate,
                          draft_fn=draft_fn, spec_stats=spec_stats, prefill_chunk=args.prefill_chunk,
-                         paged_kv=args.paged_kv)
+                         paged_kv=args.paged_kv, mxfp4=args.mxfp4_weights)
     end = sync()
     spec = {}
     if args.speculate:
@@ -220,7 +230,7 @@ def main(argv: list[str] | None = None) -> int:
                       "decode_ms_per_token": round(1000.0 * (end - marks["prefill"]) / decode_steps, 3)
                       if decode_steps else None, "stream_gemm": bool(args.stream_gemm),
                       "graph": bool(args.graph), "fp8_weights": bool(args.fp8_weights),
-                      "quantize_ms": quantize_ms, "kv_dtype": str(kv_dtype).replace("torch.", ""),
+                      "mxfp4_weights": bool(args.mxfp4_weights), "quantize_ms": quantize_ms, "kv_dtype": str(kv_dtype).replace("torch.", ""),
                       "kv_cache_mb": round(kv_bytes / 2 ** 20, 1), "prefill_chunk": args.prefill_chunk,
                       **spec, **paged}), flush=True)
     return 0
