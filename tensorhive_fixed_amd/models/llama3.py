@@ -39,6 +39,7 @@ from ..ops.embedding import embedding
 from ..ops.extend_attention import extend_attention, rope_append_block
 from ..ops.linear import linear
 from ..ops.mlp import gate_up_swiglu
+from ..ops.paged_chunk_attention import paged_chunk_attention, paged_rope_append_chunk
 from ..ops.rmsnorm import rmsnorm, rmsnorm_add_fork, rmsnorm_fork
 from ..ops.swiglu import swiglu
 
@@ -236,8 +237,8 @@ class Llama(nn.Module):
     @staticmethod
     def _refuse_paged(cache, what: str) -> None:
         if getattr(cache, "is_paged", False):
-            raise ValueError(f"Llama.{what}: a paged KV cache (PagedKVCache) runs prefill and decode_step only; "
-                             f"{what} has no paged kernel")
+            raise ValueError(f"Llama.{what}: a paged KV cache (PagedKVCache) runs prefill, prefill_paged_chunk and "
+                             f"decode_step only; {what} has no paged kernel")
 
     @torch.no_grad()
     def prefill(self, tokens: torch.Tensor, prompt_lens, cache: KVCache) -> torch.Tensor:
@@ -312,6 +313,52 @@ class Llama(nn.Module):
         cache.set_lens([a + n for a, n in zip(cache.lens, new)])
         rows = torch.tensor([b * T + max(n, 1) - 1 for b, n in enumerate(new)], device=tokens.device)
         return rmsnorm_add_fork(pending[rows].contiguous(), x[rows].contiguous(), self.norm, c.norm_eps)[0]
+
+    @torch.no_grad()
+    def prefill_paged_chunk(self, tokens: torch.Tensor, new_lens, cache, seqs=None) -> torch.Tensor:
+        """``prefill_chunk`` on a ``PagedKVCache`` for the sequences ``seqs`` (``n`` distinct indices, default all
+        of ``cache.batch`` in order): continue them by the left-aligned chunk ``tokens [n, T]``, of which the first
+        ``new_lens[i]`` tokens of sequence ``seqs[i]`` are live, with ``paged_rope_append_chunk`` /
+        ``paged_chunk_attention`` (``ops/paged_chunk_attention.py``).  This is how a prompt's suffix gets behind a
+        prefix shared with ``cache.share_prefix``, and how the prefix itself is computed for one sequence alone.
+        The pages of the new rows are reserved here.  Moves only the lengths of ``seqs``, by ``new_lens``, on host
+        and device, and returns the final-norm hidden state ``[n, dim]`` at row ``new_lens[i] - 1``."""
+        self._need_add_norm("prefill_paged_chunk")
+        c = self.cfg
+        if not getattr(cache, "is_paged", False):
+            raise ValueError("prefill_paged_chunk: needs a PagedKVCache; prefill_chunk takes the dense cache")
+        seqs = list(range(cache.batch)) if seqs is None else [int(s) for s in seqs]
+        if tokens.dim() != 2 or tokens.shape[0] != len(seqs) or tokens.shape[1] < 1:
+            raise ValueError(f"prefill_paged_chunk: expected token ids [{len(seqs)}, T >= 1], got shape "
+                             f"{tuple(tokens.shape)}")
+        B, T = tokens.shape
+        new = [int(n) for n in new_lens]
+        new_dev = torch.tensor(new, dtype=torch.int32, device=tokens.device)  # one upload for all layers
+        x = embedding(tokens, self.tok_emb).view(B * T, c.dim)
+        pending = None
+        for i, blk in enumerate(self.layers):
+            if pending is None:
+                h, x = _norm(x, blk.attn_norm, c.norm_eps)
+            else:
+                h, x = rmsnorm_add_fork(pending, x, blk.attn_norm, c.norm_eps)
+            # the ops check new_lens and seqs against the cache before anything is written (layer 0)
+            q = paged_rope_append_chunk(linear(h, blk.wqkv).view(B, T, -1), cache, i, new, new_dev, seqs=seqs)
+            o = paged_chunk_attention(q, cache, i, new, new_dev, seqs=seqs).view(B * T, -1)
+            h, x = rmsnorm_add_fork(linear(o, blk.wo), x, blk.ffn_norm, c.norm_eps)
+            pending = linear(swiglu(linear(h, blk.w13)), blk.w2)
+        cache.advance_seqs(seqs, new, new_dev)
+        rows = torch.tensor([b * T + max(n, 1) - 1 for b, n in enumerate(new)], device=tokens.device)
+        return rmsnorm_add_fork(pending[rows].contiguous(), x[rows].contiguous(), self.norm, c.norm_eps)[0]
+
+    def _prefill_shared_prefix(self, tokens: torch.Tensor, lens: list[int], S: int, P: int, cache) -> torch.Tensor:
+        """The prompts ``tokens[:, :S]``, equal in their first ``P`` tokens (whole pages), into the empty paged
+        ``cache``: sequence 0 prefills the prefix alone, the others share its pages, and one chunk over all
+        sequences takes the suffixes -> last-token hidden states ``[B, dim]``."""
+        self.prefill_paged_chunk(tokens[:1, :P].contiguous(), [P], cache, seqs=[0])
+        for b in range(1, len(lens)):
+            cache.share_prefix(0, b, P)
+        live = torch.arange(P, S, device=tokens.device)[None, :] < torch.tensor(lens, device=tokens.device)[:, None]
+        return self.prefill_paged_chunk((tokens[:, P:S] * live).contiguous(), [n - P for n in lens], cache)
 
     def _prefill_prompts(self, tokens: torch.Tensor, lens: list[int], S: int, cache: KVCache,
                          prefill_chunk: int | None) -> torch.Tensor:
@@ -595,7 +642,8 @@ class Llama(nn.Module):
                  generator: torch.Generator | None = None, return_logits: bool = False,
                  on_step=None, stream_gemm: bool = False, graph: bool = False, fp8: bool = False,
                  kv_fp8: bool = False, speculate: int = 0, draft_fn=None, spec_stats: dict | None = None,
-                 prefill_chunk: int | None = None, paged_kv: bool = False, mxfp4: bool = False):
+                 prefill_chunk: int | None = None, paged_kv: bool = False, mxfp4: bool = False,
+                 shared_prefix: int | None = None):
         """Continue the left-aligned prompts ``tokens [B, S]`` (``prompt_lens`` defaults to ``S`` for all)
         by ``max_new_tokens`` tokens -> ids ``[B, max_new_tokens]`` (and the f32 logits
         ``[B, max_new_tokens, vocab]`` of every step with ``return_logits``).  ``on_step(i)`` is called
@@ -618,6 +666,12 @@ class Llama(nn.Module):
         ``sum_b ceil((lens[b] + max_new_tokens) / 64)`` pages, every sequence's pages reserved before the
         prefill, instead of ``B * (max(lens) + max_new_tokens)`` rows; it runs the plain loop and refuses
         ``graph``, ``kv_fp8``, ``speculate`` and ``prefill_chunk``.
+        ``shared_prefix = N`` (with ``paged_kv``) says the first ``N`` tokens of every prompt are the same (checked on
+        the host; ``1 <= N < min(lens)``).  Their page-aligned part ``P = (N // 64) * 64`` is prefilled once, by
+        sequence 0 alone (``prefill_paged_chunk(..., seqs=[0])``), the other sequences share its pages
+        (``share_prefix``) and one ``prefill_paged_chunk`` over all sequences takes the suffixes; the pool holds
+        ``ceil(P / 64) + sum_b ceil((lens[b] + max_new_tokens - P) / 64)`` pages.  ``P == 0`` runs the plain paged
+        path.  It refuses what ``paged_kv`` refuses.
         ``mxfp4`` runs the decode steps on MXFP4 weights (``decode_step(mxfp4=True)``), quantizing them first
         if ``quantize_decode_weights_mxfp4()`` has not been called; it composes with ``stream_gemm`` (ignored),
         ``graph``, ``kv_fp8`` and ``paged_kv``, which touch only attention, and refuses ``fp8``, ``speculate``
@@ -630,6 +684,8 @@ class Llama(nn.Module):
             if tokens.shape[0] > 16:
                 raise ValueError(f"generate: mxfp4 with batch {tokens.shape[0]} is above the 16 rows of the MXFP4 "
                                  "decode kernel")
+        if shared_prefix is not None and not paged_kv:
+            raise ValueError("generate: shared_prefix needs paged_kv=True: only a paged KV cache shares rows")
         if paged_kv:
             for name, on in (("graph", graph), ("kv_fp8", kv_fp8), ("speculate", speculate),
                              ("prefill_chunk", prefill_chunk is not None)):
@@ -664,17 +720,29 @@ class Llama(nn.Module):
             self.quantize_decode_weights_mxfp4()
         if len(lens) != B or min(lens) < 1 or S > tokens.shape[1]:
             raise ValueError(f"generate: prompt lengths {lens} do not fit tokens of shape {tuple(tokens.shape)}")
+        P = 0
+        if shared_prefix is not None:
+            N = int(shared_prefix)
+            if N < 1 or N >= min(lens):
+                raise ValueError(f"generate: shared_prefix {N} must be in [1, {min(lens)}): at least one token of every "
+                                 "prompt follows the prefix")
+            if not bool((tokens[:, :N] == tokens[:1, :N]).all()):
+                raise ValueError(f"generate: shared_prefix {N}: the prompts differ inside their first {N} tokens")
+            P = N // 64 * 64  # whole pages: the rows behind them start a page of their own
         if paged_kv:
             from ..ops.paged_attention import PagedKVCache, pages_for
 
-            cache = PagedKVCache(self.cfg, B, max_len, sum(pages_for(n + max_new_tokens) for n in lens),
-                                 tokens.device)
+            cache = PagedKVCache(self.cfg, B, max_len,
+                                 pages_for(P) + sum(pages_for(n + max_new_tokens - P) for n in lens), tokens.device)
+            if P:
+                h = self._prefill_shared_prefix(tokens, lens, S, P, cache)
             for b, n in enumerate(lens):  # up front: the table does not change during decode
                 cache.reserve(b, n + max_new_tokens)
         else:
             cache = KVCache(self.cfg, B, max_len, tokens.device,
                             dtype=torch.float8_e4m3fn if kv_fp8 else torch.bfloat16)
-        h = self._prefill_prompts(tokens, lens, S, cache, prefill_chunk)  # token 0 after every prompt
+        if not P:
+            h = self._prefill_prompts(tokens, lens, S, cache, prefill_chunk)  # token 0 after every prompt
         logits = torch.mm(h, self.lm_head.t()).float()
         captured = (self.decode_graph(cache, stream_gemm=stream_gemm, fp8=fp8, mxfp4=mxfp4)
                     if graph and max_new_tokens > 1 else None)

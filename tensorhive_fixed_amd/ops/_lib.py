@@ -63,6 +63,9 @@ _SIGS: dict[str, list] = {
     "th_chunk_attn_split": [P, P, P, P, P, P, P, I, I, I, I, I, I, L, L, I, F, P],
     "th_paged_rope_append": [P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, L, L, P],
     "th_paged_decode_attn": [P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, L, L, I, I, I, F, P],
+    "th_paged_chunk_rope_append": [P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, L, L, P],
+    "th_paged_chunk_attn": [P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, L, L, F, P],
+    "th_paged_chunk_attn_split": [P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, L, L, I, F, P],
     "th_decode_linear": [P, P, P, I, L, I, I, I, P],
     "th_decode_linear_fp8": [P, P, P, P, I, L, I, I, I, P],
     "th_decode_linear_mxfp4": [P, P, P, P, I, L, I, I, I, P],

@@ -61,6 +61,23 @@
 //   others by exp2(m_s - max m) in split order, swaps halves with lane L ^ 32 (which holds the other 4 of
 //   every 8 dims of the same row) and writes 2 x 16 bytes of bf16; rows t >= new_len[b] and rows with no
 //   key are exact zeros.  No atomic and no counter: two runs give the same bits.
+//
+// th_paged_chunk_rope_append / th_paged_chunk_attn / th_paged_chunk_attn_split    the same three on the PAGED
+//   cache of paged_attn.hip: pool [n_pages, Hkv, 64, 128] per K / V, table [B, table_stride] int32, logical row r
+//   of sequence b in row r & 63 of page table[b][r >> 6].  A page is KTILE rows, so key tile j of sequence b IS
+//   page table[b][j]: one contiguous 16 KB run per KV head.  chunk_attn_kernel<SPLIT, true> keeps the grid, the
+//   images, the MFMA products, the masks, the softmax and the epilogues of the dense kernel and changes only how
+//   a tile's rows are found, so it gives the dense kernel's bits on the same rows through any table:
+//     the page id of a tile is workgroup-uniform: a scalar load from table + b * table_stride, clamped to
+//     [0, n_pages) (a bad id is never followed) and turned into the 64-bit pool offset id * stride_page +
+//     hkv * stride_h, all in SGPRs; a lane adds a 32-bit offset inside the 16 KB run (row x 256 B + its chunk).
+//     The global loads of tile j + 2 are issued in iteration j, so the entry of tile j + 2 is read in
+//     iteration j - 1 (that of j + 3 in iteration j, right behind the loads) and clamped only where it is used:
+//     the key loop never waits on a table entry.  Only the entries of the workgroup's own tiles [j0, j1) are
+//     read (the read-ahead index is clamped to j1 - 1), never one at or past ceil(kv_end / 64).  Rows past
+//     kv_end - 1 of the last tile come from row kv_end - 1, which lies in the same page.  The append checks the
+//     page id against [0, n_pages) before an address is formed: a row whose id fails stores nothing in the pool,
+//     its q still goes out.
 #include "th_common.h"
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -68,6 +85,7 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef short i16x4 __attribute__((ext_vector_type(4)));
 typedef short i16x8 __attribute__((ext_vector_type(8)));
 #define LDS_AS __attribute__((address_space(3)))
+#define CONST_AS __attribute__((address_space(4)))
 
 namespace {
 
@@ -154,17 +172,27 @@ __device__ __forceinline__ void chunk_lens(const int* kv_len, const int* new_len
   nw = n > Smax - l ? Smax - l : n;
 }
 
+// the page table of a paged launch: the first member of the kernels' trailing argument pack
+struct PageMap {
+  const int* table;
+  int n_pages, table_stride;
+};
+
 __device__ __forceinline__ float* split_ws(float* ws, int) { return ws; }
 __device__ __forceinline__ int split_count(float*, int nsplit) { return nsplit; }
+__device__ __forceinline__ float* split_ws(PageMap, float* ws, int) { return ws; }
+__device__ __forceinline__ int split_count(PageMap, float*, int nsplit) { return nsplit; }
+template <typename... R>
+__device__ __forceinline__ PageMap page_map(PageMap pm, R...) { return pm; }
 
 // a row's (m, l) = (-inf, 0): the neutral partial, which the combine pass skips
 __device__ __forceinline__ void store_neutral(float* slot, int w, int c32, int h) {
   if (h == 0) *reinterpret_cast<float2*>(slot + 2 * (w * 32 + c32)) = make_float2(-INFINITY, 0.f);
 }
 
-// SPLIT: `sp...` is (float* ws, int nsplit) and `o` is not written; otherwise there is no `sp` and the
-// argument block is that of the unsplit kernel
-template <bool SPLIT, typename... SP>
+// SPLIT: `sp...` ends in (float* ws, int nsplit) and `o` is not written.  PAGED: `sp...` starts with a PageMap,
+// kc / vc are the pools and stride_b is the page stride.  <false, false> has no `sp`.
+template <bool SPLIT, bool PAGED, typename... SP>
 __global__ __launch_bounds__(256, 2) void chunk_attn_kernel(
     const ushort* __restrict__ q, const ushort* __restrict__ kc, const ushort* __restrict__ vc,
     const int* __restrict__ kv_len, const int* __restrict__ new_len, ushort* __restrict__ o, int T, int Hq,
@@ -239,12 +267,41 @@ __global__ __launch_bounds__(256, 2) void chunk_attn_kernel(
   const ushort* kb = kc + b * stride_b + hkv * stride_h + sch * 8;
   const ushort* vb = vc + b * stride_b + hkv * stride_h + sch * 8;
   ushort8 kr[4], vr[4];
-  auto load_tile = [&](int j) {  // rows past the loop's end come from its last row (live) and are masked
+  // PAGED: the table entry of key tile min(j, j1 - 1), scalar and still unclamped (the clamp waits for the load,
+  // so it is left to the entry's use).  Only entries of [j0, j1) are read: they exist (j1 <= ceil(Smax / 64) <=
+  // table_stride) and belong to the sequence.
+  auto page_id = [&](int j) -> int {
+    if constexpr (PAGED) {
+      const PageMap pm = page_map(sp...);
+      // read through the constant address space: nothing writes the table while the kernel runs, and the split
+      // form's workspace stores would otherwise turn this scalar load into a vector load the loop waits on
+      const CONST_AS int* trow = (const CONST_AS int*)pm.table + (long)b * pm.table_stride;
+      return __builtin_amdgcn_readfirstlane(trow[min(j, j1 - 1)]);
+    }
+    return 0;
+  };
+  // rows past the loop's end come from its last row (live, and in the same page) and are masked
+  auto load_tile = [&](int j, int id) {
+    if constexpr (PAGED) {
+      const int n_pages = page_map(sp...).n_pages;
+      id = id < 0 ? 0 : (id >= n_pages ? n_pages - 1 : id);  // a bad id is clamped, never followed
+      const long off = (long)id * stride_b + hkv * stride_h;  // the (page, kv head) run: 64 bits, scalar
+      const char* kp = reinterpret_cast<const char*>(kc + off);
+      const char* vp = reinterpret_cast<const char*>(vc + off);
+      const int last = kv_end - 1 - j * KTILE;  // >= 63 except in the last tile
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const long row = min(j * KTILE + 16 * i + srow, kv_end - 1);
-      kr[i] = *reinterpret_cast<const ushort8*>(kb + row * DH);
-      vr[i] = *reinterpret_cast<const ushort8*>(vb + row * DH);
+      for (int i = 0; i < 4; ++i) {
+        const unsigned x = (unsigned)min(16 * i + srow, last) * (DH * 2) + sch * 16;  // inside the 16 KB run
+        kr[i] = *reinterpret_cast<const ushort8*>(kp + x);
+        vr[i] = *reinterpret_cast<const ushort8*>(vp + x);
+      }
+    } else {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const long row = min(j * KTILE + 16 * i + srow, kv_end - 1);
+        kr[i] = *reinterpret_cast<const ushort8*>(kb + row * DH);
+        vr[i] = *reinterpret_cast<const ushort8*>(vb + row * DH);
+      }
     }
   };
   auto store_tile = [&](int buf) {
@@ -256,9 +313,18 @@ __global__ __launch_bounds__(256, 2) void chunk_attn_kernel(
     }
   };
 
-  load_tile(j0);
-  store_tile(j0 & 1);
-  if (j0 + 1 < j1) load_tile(j0 + 1);
+  int pnext = 0;  // PAGED: page_id of the tile whose loads are issued next, read one iteration before them
+  if constexpr (PAGED) {
+    const int p0 = page_id(j0), p1 = page_id(j0 + 1);
+    pnext = page_id(j0 + 2);
+    load_tile(j0, p0);
+    store_tile(j0 & 1);
+    if (j0 + 1 < j1) load_tile(j0 + 1, p1);
+  } else {
+    load_tile(j0, 0);
+    store_tile(j0 & 1);
+    if (j0 + 1 < j1) load_tile(j0 + 1, 0);
+  }
   __syncthreads();
 
   float m_i = -INFINITY, l_i = 0.f;  // l_i: this lane's 32 keys per tile; the pair is summed at the end
@@ -266,8 +332,9 @@ __global__ __launch_bounds__(256, 2) void chunk_attn_kernel(
     // the other image was last read in iteration j - 1, which ended with a barrier
     if (j + 1 < j1) {
       store_tile((j + 1) & 1);
-      if (j + 2 < j1) load_tile(j + 2);
+      if (j + 2 < j1) load_tile(j + 2, pnext);
     }
+    if constexpr (PAGED) pnext = page_id(j + 3);  // right behind the loads of tile j + 2, used in iteration j + 1
     const int kbase = j * KTILE;
     if (wave_live && kbase < wlast) {  // wave-uniform
       const char* ks = smem + (j & 1) * (2 * IMG);
@@ -395,11 +462,13 @@ __global__ __launch_bounds__(256) void chunk_attn_combine_kernel(
   }
 }
 
+// PAGED: `pg` is one PageMap, kc / vc are the pools and stride_b is the page stride
+template <bool PAGED, typename... PG>
 __global__ __launch_bounds__(256) void chunk_rope_append_kernel(
     const ushort* __restrict__ qkv, const int* __restrict__ kv_len, const int* __restrict__ new_len,
     const float* __restrict__ cosT, const float* __restrict__ sinT, ushort* __restrict__ q_out,
     ushort* __restrict__ kc, ushort* __restrict__ vc, int T, int Hq, int Hkv, int Smax, long stride_b,
-    long stride_h) {
+    long stride_h, PG... pg) {
   const long bt = blockIdx.x;
   const int b = (int)(bt / T), t = (int)(bt - (long)b * T);
   int len0, nw;
@@ -410,6 +479,14 @@ __global__ __launch_bounds__(256) void chunk_rope_append_kernel(
     return;
   }
   const int p = len0 + t;  // < Smax by the clamp: never a table or cache row out of range
+  long row = b * stride_b + (long)p * DH;  // of KV head 0
+  bool stored = true;
+  if constexpr (PAGED) {
+    const PageMap pm = page_map(pg...);
+    const int id = pm.table[(long)b * pm.table_stride + (p >> 6)];  // p >> 6 < ceil(Smax / 64) <= table_stride
+    stored = id >= 0 && id < pm.n_pages;  // a bad id: nothing of this row goes to the pool
+    row = stored ? (long)id * stride_b + (long)(p & 63) * DH : 0;
+  }
   const ushort* in = qkv + bt * (Hq + 2 * Hkv) * DH;
   const int nrot = (Hq + Hkv) * 8;    // 8-pair chunks of the rotated heads
   const int total = nrot + Hkv * 16;  // + 16-byte chunks of v
@@ -430,14 +507,14 @@ __global__ __launch_bounds__(256) void chunk_rope_append_kernel(
         y1[j] = f2bf(a * cs[j] - bb * sn[j]);
         y2[j] = f2bf(bb * cs[j] + a * sn[j]);
       }
-      ushort* out = hd < Hq ? q_out + (bt * Hq + hd) * DH
-                            : kc + b * stride_b + (hd - Hq) * stride_h + (long)p * DH;
+      if (hd >= Hq && !stored) continue;
+      ushort* out = hd < Hq ? q_out + (bt * Hq + hd) * DH : kc + row + (hd - Hq) * stride_h;
       *reinterpret_cast<ushort8*>(out + c * 8) = y1;
       *reinterpret_cast<ushort8*>(out + 64 + c * 8) = y2;
-    } else {
+    } else if (stored) {
       const int hd = (i - nrot) >> 4, c = (i - nrot) & 15;
       const ushort8 x = *reinterpret_cast<const ushort8*>(in + (Hq + Hkv + hd) * DH + c * 8);
-      *reinterpret_cast<ushort8*>(vc + b * stride_b + hd * stride_h + (long)p * DH + c * 8) = x;
+      *reinterpret_cast<ushort8*>(vc + row + hd * stride_h + c * 8) = x;
     }
   }
 }
@@ -453,6 +530,22 @@ bool chunk_geometry_ok(int B, int T, int Hq, int Hkv, int Dh, int Smax, long str
   return true;
 }
 
+// chunk_geometry_ok for a pool: every row of a sequence has a table entry; the table's rows, the pages and the
+// heads of a page do not overlap
+bool paged_chunk_geometry_ok(int B, int T, int Hq, int Hkv, int Dh, int Smax, int n_pages, int max_pages,
+                             int table_stride, long stride_page, long stride_h) {
+  if (Dh != DH || B <= 0 || B > 65535 || T < 1 || T > (1 << 24) || (long)B * T > 0x7fffffffL || Hq <= 0 ||
+      Hkv <= 0 || Hkv > 65535 || Hq % Hkv || Smax <= 0 || Smax > (1 << 30))
+    return false;
+  const int rep = Hq / Hkv;
+  if (rep != 1 && rep != 2 && rep != 4 && rep != 8) return false;
+  if (n_pages <= 0 || max_pages <= 0 || (long)max_pages * KTILE < Smax || table_stride < max_pages) return false;
+  if (stride_h % 8 || stride_page % 8 || stride_h < (long)KTILE * DH || stride_page < Hkv * stride_h) return false;
+  return true;
+}
+
+int rep_shift_of(int rep) { return rep == 1 ? 0 : rep == 2 ? 1 : rep == 4 ? 2 : 3; }
+
 }  // namespace
 
 extern "C" int th_chunk_rope_append(const void* qkv, const int* kv_len, const int* new_len, const float* cosT,
@@ -460,7 +553,7 @@ extern "C" int th_chunk_rope_append(const void* qkv, const int* kv_len, const in
                                     int Hq, int Hkv, int Dh, int Smax, long stride_b, long stride_h,
                                     hipStream_t s) {
   if (!chunk_geometry_ok(B, T, Hq, Hkv, Dh, Smax, stride_b, stride_h)) return -1;
-  chunk_rope_append_kernel<<<B * T, 256, 0, s>>>((const ushort*)qkv, kv_len, new_len, cosT, sinT,
+  chunk_rope_append_kernel<false><<<B * T, 256, 0, s>>>((const ushort*)qkv, kv_len, new_len, cosT, sinT,
                                                  (ushort*)q_out, (ushort*)kcache, (ushort*)vcache, T, Hq, Hkv,
                                                  Smax, stride_b, stride_h);
   TH_CHECK_LAUNCH();
@@ -476,7 +569,7 @@ extern "C" int th_chunk_attn(const void* q, const void* kcache, const void* vcac
   const int rep_shift = rep == 1 ? 0 : rep == 2 ? 1 : rep == 4 ? 2 : 3;
   const dim3 grid((T * rep + QTILE - 1) / QTILE, Hkv, B);
   const float qscale = scale * 1.4426950408889634f;  // scores in the base-2 domain
-  chunk_attn_kernel<false><<<grid, 256, 0, s>>>((const ushort*)q, (const ushort*)kcache, (const ushort*)vcache, kv_len,
+  chunk_attn_kernel<false, false><<<grid, 256, 0, s>>>((const ushort*)q, (const ushort*)kcache, (const ushort*)vcache, kv_len,
                                          new_len, (ushort*)o, T, Hq, Smax, stride_b, stride_h, rep_shift, qscale);
   TH_CHECK_LAUNCH();
 }
@@ -492,9 +585,62 @@ extern "C" int th_chunk_attn_split(const void* q, const void* kcache, const void
   const int rep_shift = rep == 1 ? 0 : rep == 2 ? 1 : rep == 4 ? 2 : 3;
   const int qtiles = (int)(((long)T * rep + QTILE - 1) / QTILE);
   const float qscale = scale * 1.4426950408889634f;  // scores in the base-2 domain
-  chunk_attn_kernel<true><<<dim3(qtiles * nsplit, Hkv, B), 256, 0, s>>>(
+  chunk_attn_kernel<true, false><<<dim3(qtiles * nsplit, Hkv, B), 256, 0, s>>>(
       (const ushort*)q, (const ushort*)kcache, (const ushort*)vcache, kv_len, new_len, (ushort*)o, T, Hq, Smax,
       stride_b, stride_h, rep_shift, qscale, (float*)ws, nsplit);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return (int)e;
+  chunk_attn_combine_kernel<<<dim3(qtiles * 4, Hkv, B), 256, 0, s>>>((const float*)ws, kv_len, new_len, (ushort*)o,
+                                                                     T, Hq, Smax, rep_shift, nsplit);
+  TH_CHECK_LAUNCH();
+}
+
+// th_chunk_rope_append through the page table: row p = kv_len[b] + t goes to row p & 63 of page table[b][p >> 6].
+extern "C" int th_paged_chunk_rope_append(const void* qkv, const int* kv_len, const int* new_len, const int* table,
+                                          const float* cosT, const float* sinT, void* q_out, void* kpool,
+                                          void* vpool, int B, int T, int Hq, int Hkv, int Dh, int Smax, int n_pages,
+                                          int max_pages, int table_stride, long stride_page, long stride_h,
+                                          hipStream_t s) {
+  if (!paged_chunk_geometry_ok(B, T, Hq, Hkv, Dh, Smax, n_pages, max_pages, table_stride, stride_page, stride_h))
+    return -1;
+  chunk_rope_append_kernel<true><<<B * T, 256, 0, s>>>((const ushort*)qkv, kv_len, new_len, cosT, sinT,
+                                                       (ushort*)q_out, (ushort*)kpool, (ushort*)vpool, T, Hq, Hkv,
+                                                       Smax, stride_page, stride_h,
+                                                       PageMap{table, n_pages, table_stride});
+  TH_CHECK_LAUNCH();
+}
+
+// th_chunk_attn on the pool: the rows of sequence b are those its table row names; the bits of th_chunk_attn.
+extern "C" int th_paged_chunk_attn(const void* q, const void* kpool, const void* vpool, const int* table,
+                                   const int* kv_len, const int* new_len, void* o, int B, int T, int Hq, int Hkv,
+                                   int Dh, int Smax, int n_pages, int max_pages, int table_stride, long stride_page,
+                                   long stride_h, float scale, hipStream_t s) {
+  if (!paged_chunk_geometry_ok(B, T, Hq, Hkv, Dh, Smax, n_pages, max_pages, table_stride, stride_page, stride_h))
+    return -1;
+  const int rep = Hq / Hkv;
+  const dim3 grid((int)(((long)T * rep + QTILE - 1) / QTILE), Hkv, B);
+  const float qscale = scale * 1.4426950408889634f;  // scores in the base-2 domain
+  chunk_attn_kernel<false, true><<<grid, 256, 0, s>>>(
+      (const ushort*)q, (const ushort*)kpool, (const ushort*)vpool, kv_len, new_len, (ushort*)o, T, Hq, Smax,
+      stride_page, stride_h, rep_shift_of(rep), qscale, PageMap{table, n_pages, table_stride});
+  TH_CHECK_LAUNCH();
+}
+
+// th_chunk_attn_split on the pool (ws as there); the bits of th_chunk_attn_split at the same nsplit.
+extern "C" int th_paged_chunk_attn_split(const void* q, const void* kpool, const void* vpool, const int* table,
+                                         const int* kv_len, const int* new_len, void* o, void* ws, int B, int T,
+                                         int Hq, int Hkv, int Dh, int Smax, int n_pages, int max_pages,
+                                         int table_stride, long stride_page, long stride_h, int nsplit, float scale,
+                                         hipStream_t s) {
+  if (!paged_chunk_geometry_ok(B, T, Hq, Hkv, Dh, Smax, n_pages, max_pages, table_stride, stride_page, stride_h) ||
+      nsplit < 2 || nsplit > MAX_CHUNK_SPLITS)
+    return -1;
+  const int rep = Hq / Hkv, rep_shift = rep_shift_of(rep);
+  const int qtiles = (int)(((long)T * rep + QTILE - 1) / QTILE);
+  const float qscale = scale * 1.4426950408889634f;  // scores in the base-2 domain
+  chunk_attn_kernel<true, true><<<dim3(qtiles * nsplit, Hkv, B), 256, 0, s>>>(
+      (const ushort*)q, (const ushort*)kpool, (const ushort*)vpool, kv_len, new_len, (ushort*)o, T, Hq, Smax,
+      stride_page, stride_h, rep_shift, qscale, PageMap{table, n_pages, table_stride}, (float*)ws, nsplit);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return (int)e;
   chunk_attn_combine_kernel<<<dim3(qtiles * 4, Hkv, B), 256, 0, s>>>((const float*)ws, kv_len, new_len, (ushort*)o,

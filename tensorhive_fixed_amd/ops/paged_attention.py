@@ -20,8 +20,11 @@ GPU tensors run the gfx950 kernels (a missing entry point raises); CPU tensors r
 references below: the rows gathered through the table, then the math of the dense references, so a
 paged and a dense cache with the same content give the same bits on the CPU.
 
-Not supported (each raises ``ValueError``): an FP8 pool, block / chunk steps, and the device-geometry
-form a captured graph needs.
+Chunk steps (a block of new tokens per sequence, for a subset of the sequences: the prompt suffixes behind
+a shared prefix) are in ``ops/paged_chunk_attention.py``; ``seq_view`` and ``advance_seqs`` below serve them.
+
+Not supported (each raises ``ValueError``): an FP8 pool, block steps (``extend_attention``), appending into
+a page that is still shared (no copy-on-write), and the device-geometry form a captured graph needs.
 """
 from __future__ import annotations
 
@@ -76,11 +79,12 @@ class PagedKVCache:
         self.lens_dev = torch.zeros(batch, device=self.device, dtype=torch.int32)
         self._ws: torch.Tensor | None = None
         self._scatter: tuple | None = None  # fill's index tensors, dropped when the table changes
+        self._view: tuple | None = None  # seq_view's gathered rows, dropped when a table row or a length changes
 
     # ------------------------------------------------------------------ allocation (host)
     def _upload(self, b: int) -> None:
         self.table_dev[b, : len(self.table[b])] = torch.tensor(self.table[b], dtype=torch.int32)
-        self._scatter = None
+        self._scatter = self._view = None
 
     def reserve(self, b: int, rows: int) -> None:
         """Pages for at least ``rows`` rows of sequence ``b``; raises, with nothing changed, when the pool
@@ -107,7 +111,7 @@ class PagedKVCache:
             if self._refs[p] == 0:
                 self.free_pages.append(p)
         self.table[b] = []
-        self._scatter = None
+        self._scatter = self._view = None
         self.lens[b] = 0
         self.lens_dev[b] = 0
 
@@ -182,12 +186,38 @@ class PagedKVCache:
                              f"({[self.owned_rows(b) for b in range(self.batch)]}): reserve() first")
         self.lens = lens
         self.lens_dev.copy_(torch.tensor(lens, dtype=torch.int32))
+        self._view = None
 
     def advance(self, n: int = 1) -> None:
         if max(self.lens) + n > self.max_len:
             raise ValueError(f"PagedKVCache: {max(self.lens)} + {n} rows exceed max_len {self.max_len}")
         self.lens = [x + n for x in self.lens]
         self.lens_dev += n
+        self._view = None
+
+    def seq_view(self, seqs) -> tuple[torch.Tensor, torch.Tensor]:
+        """``(lens_dev[seqs], table_dev[seqs])``, contiguous: what a kernel that serves only the sequences
+        ``seqs`` takes as its lengths and its table.  Gathered once and kept until a length or a table row
+        changes, so the layers of a model step share it; all sequences in order get the tensors themselves."""
+        key = tuple(seqs)
+        if key == tuple(range(self.batch)):
+            return self.lens_dev, self.table_dev
+        if self._view is None or self._view[0] != key:
+            idx = torch.tensor(key, dtype=torch.long, device=self.device)
+            self._view = (key, self.lens_dev[idx].contiguous(), self.table_dev[idx].contiguous())
+        return self._view[1], self._view[2]
+
+    def advance_seqs(self, seqs, new, new_dev: torch.Tensor | None = None) -> None:
+        """Move the lengths of the sequences ``seqs`` only, by ``new[i]`` rows each, on host and device."""
+        if any(self.lens[s] + n > min(self.max_len, self.owned_rows(s)) for s, n in zip(seqs, new) if n):
+            raise ValueError(f"PagedKVCache: lengths {[self.lens[s] for s in seqs]} + {list(new)} exceed max_len "
+                             f"{self.max_len} or the rows the sequences own")
+        for s, n in zip(seqs, new):
+            self.lens[s] += n
+        if new_dev is None:
+            new_dev = torch.tensor(list(new), dtype=torch.int32, device=self.device)
+        self.lens_dev.index_add_(0, torch.tensor(list(seqs), dtype=torch.long, device=self.device), new_dev)
+        self._view = None
 
     def advance_host(self, n: int = 1) -> None:
         if max(self.lens) + n > self.max_len:

@@ -30,6 +30,11 @@ with ``--fp8-kv``.
 ``ceil((prompt + new tokens) / 64)`` of them instead of the longest sequence's rows); ``kv_cache_mb`` is then the
 pool and ``kv_dense_mb`` what the dense cache would have taken.  Not with ``--graph``, ``--fp8-kv``, ``--speculate``
 or ``--prefill-chunk``.
+``--shared-prefix N`` (needs ``--paged-kv``) says the first N tokens of every prompt are the same: the synthetic
+prompts are made so, prompts from ``--prompt-ids`` are checked.  The page-aligned part of the prefix is prefilled
+once and its pages are shared by every sequence (``Llama.generate(shared_prefix=N)``,
+``ops/paged_chunk_attention.py``); the JSON line then carries ``shared_prefix``, ``kv_pages`` (the pool) and
+``prefix_pages`` (the shared part of it) beside ``prefill_ms``.
 ``--repeat-prompt N`` makes the synthetic prompts repeat an N-token pattern, which prompt lookup can use.
 
 The project has no tokenizer: prompts are token ids, from ``--prompt-ids FILE`` (a JSON list of id
@@ -145,6 +150,9 @@ def main(argv: list[str] | None = None) -> int:
     ap.add_argument("--paged-kv", action="store_true",
                     help="keep the KV rows in a paged cache (ops/paged_attention.py, csrc/paged_attn.hip); not with "
                          "--graph, --fp8-kv, --speculate or --prefill-chunk")
+    ap.add_argument("--shared-prefix", type=int, default=None, metavar="N",
+                    help="the first N tokens of every prompt are the same: prefill their whole pages once and share "
+                         "them (ops/paged_chunk_attention.py); needs --paged-kv")
     ap.add_argument("--repeat-prompt", type=int, default=0, metavar="N",
                     help="synthetic prompts repeat an N-token pattern")
     args = ap.parse_args(argv)
@@ -158,6 +166,11 @@ def main(argv: list[str] | None = None) -> int:
         load_checkpoint_params(model, args.ckpt)
     tokens, lens = _prompts(args, cfg, device)
     batch = tokens.shape[0]
+    if args.shared_prefix is not None:
+        if not args.paged_kv:
+            ap.error("--shared-prefix needs --paged-kv")
+        if not args.prompt_ids:
+            tokens[:, : args.shared_prefix] = tokens[:1, : args.shared_prefix]
     sampler = torch.Generator(device=device)
     sampler.manual_seed(args.seed + 1)
 
@@ -201,7 +214,7 @@ def main(argv: list[str] | None = None) -> int:
                          top_k=args.top_k, generator=sampler, on_step=on_step, stream_gemm=args.stream_gemm,
                          graph=args.graph, fp8=args.fp8_weights, kv_fp8=args.fp8_kv, speculate=args.speculate,
                          draft_fn=draft_fn, spec_stats=spec_stats, prefill_chunk=args.prefill_chunk,
-                         paged_kv=args.paged_kv, mxfp4=args.mxfp4_weights)
+                         paged_kv=args.paged_kv, mxfp4=args.mxfp4_weights, shared_prefix=args.shared_prefix)
     end = sync()
     spec = {}
     if args.speculate:
@@ -221,8 +234,12 @@ def main(argv: list[str] | None = None) -> int:
     if args.paged_kv:
         from ..ops.paged_attention import paged_cache_bytes, pages_for
 
-        paged = {"paged_kv": True, "kv_dense_mb": round(kv_bytes / 2 ** 20, 1)}
-        kv_bytes = paged_cache_bytes(cfg, sum(pages_for(n + args.max_new_tokens) for n in lens))  # generate()'s pool
+        P = (args.shared_prefix or 0) // 64 * 64  # generate()'s pool: the shared pages once, the rest per sequence
+        n_pages = pages_for(P) + sum(pages_for(n + args.max_new_tokens - P) for n in lens)
+        paged = {"paged_kv": True, "kv_dense_mb": round(kv_bytes / 2 ** 20, 1), "kv_pages": n_pages}
+        if args.shared_prefix is not None:
+            paged.update(shared_prefix=args.shared_prefix, prefix_pages=pages_for(P))
+        kv_bytes = paged_cache_bytes(cfg, n_pages)
         print(f"[th-gen] paged KV pool {kv_bytes} bytes, the dense cache would take "
               f"{kv_cache_bytes(cfg, batch, max(lens) + args.max_new_tokens)} bytes", flush=True)
     print(json.dumps({"event": "done", "new_tokens": int(ids.numel()),
