@@ -643,7 +643,7 @@ class Llama(nn.Module):
                  on_step=None, stream_gemm: bool = False, graph: bool = False, fp8: bool = False,
                  kv_fp8: bool = False, speculate: int = 0, draft_fn=None, spec_stats: dict | None = None,
                  prefill_chunk: int | None = None, paged_kv: bool = False, mxfp4: bool = False,
-                 shared_prefix: int | None = None):
+                 shared_prefix: int | None = None, cascade: bool = False):
         """Continue the left-aligned prompts ``tokens [B, S]`` (``prompt_lens`` defaults to ``S`` for all)
         by ``max_new_tokens`` tokens -> ids ``[B, max_new_tokens]`` (and the f32 logits
         ``[B, max_new_tokens, vocab]`` of every step with ``return_logits``).  ``on_step(i)`` is called
@@ -672,6 +672,9 @@ class Llama(nn.Module):
         (``share_prefix``) and one ``prefill_paged_chunk`` over all sequences takes the suffixes; the pool holds
         ``ceil(P / 64) + sum_b ceil((lens[b] + max_new_tokens - P) / 64)`` pages.  ``P == 0`` runs the plain paged
         path.  It refuses what ``paged_kv`` refuses.
+        ``cascade`` (with ``shared_prefix``) sets ``cache.cascade_rows = P`` after that prefill: every decode step's
+        attention then reads the ``P`` shared rows once for the whole batch (``ops/paged_cascade_attention.py``)
+        instead of once per sequence.  ``P == 0`` runs the plain paged path; ``False`` leaves every path's bits alone.
         ``mxfp4`` runs the decode steps on MXFP4 weights (``decode_step(mxfp4=True)``), quantizing them first
         if ``quantize_decode_weights_mxfp4()`` has not been called; it composes with ``stream_gemm`` (ignored),
         ``graph``, ``kv_fp8`` and ``paged_kv``, which touch only attention, and refuses ``fp8``, ``speculate``
@@ -684,6 +687,9 @@ class Llama(nn.Module):
             if tokens.shape[0] > 16:
                 raise ValueError(f"generate: mxfp4 with batch {tokens.shape[0]} is above the 16 rows of the MXFP4 "
                                  "decode kernel")
+        if cascade and (shared_prefix is None or not paged_kv):
+            raise ValueError("generate: cascade needs shared_prefix=N (and paged_kv=True): cascade decode reads the "
+                             "rows that the sequences share once per batch")
         if shared_prefix is not None and not paged_kv:
             raise ValueError("generate: shared_prefix needs paged_kv=True: only a paged KV cache shares rows")
         if paged_kv:
@@ -738,6 +744,8 @@ class Llama(nn.Module):
                 h = self._prefill_shared_prefix(tokens, lens, S, P, cache)
             for b, n in enumerate(lens):  # up front: the table does not change during decode
                 cache.reserve(b, n + max_new_tokens)
+            if P and cascade:
+                cache.cascade_rows = P
         else:
             cache = KVCache(self.cfg, B, max_len, tokens.device,
                             dtype=torch.float8_e4m3fn if kv_fp8 else torch.bfloat16)

@@ -63,6 +63,7 @@ _SIGS: dict[str, list] = {
     "th_chunk_attn_split": [P, P, P, P, P, P, P, I, I, I, I, I, I, L, L, I, F, P],
     "th_paged_rope_append": [P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, L, L, P],
     "th_paged_decode_attn": [P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, L, L, I, I, I, F, P],
+    "th_paged_cascade_decode_attn": [P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, L, L, I, I, I, I, I, I, F, P],
     "th_paged_chunk_rope_append": [P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, L, L, P],
     "th_paged_chunk_attn": [P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, L, L, F, P],
     "th_paged_chunk_attn_split": [P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, L, L, I, F, P],

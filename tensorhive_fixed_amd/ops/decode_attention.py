@@ -282,6 +282,10 @@ def decode_attention(q: torch.Tensor, cache: KVCache, layer: int, nsplit: int | 
 
         if device_geometry:
             raise ValueError("decode_attention: a paged KV cache has no device_geometry form (no captured steps)")
+        if cache.cascade_rows > 0:  # the sequences share their first pages: read them once (opt-in)
+            from .paged_cascade_attention import paged_cascade_decode_attention
+
+            return paged_cascade_decode_attention(q, cache, layer, cache.cascade_rows, nsplit=nsplit, new=new)
         return paged_decode_attention(q, cache, layer, nsplit=nsplit, new=new)
     Hq, Hkv = cache.n_heads, cache.n_kv_heads
     _check(q, cache, Hq * HEAD_DIM, layer, new, "decode_attention")

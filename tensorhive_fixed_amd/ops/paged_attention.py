@@ -23,6 +23,11 @@ paged and a dense cache with the same content give the same bits on the CPU.
 Chunk steps (a block of new tokens per sequence, for a subset of the sequences: the prompt suffixes behind
 a shared prefix) are in ``ops/paged_chunk_attention.py``; ``seq_view`` and ``advance_seqs`` below serve them.
 
+Cascade decode (opt-in): with ``cache.cascade_rows = P`` (whole pages that every sequence shares, checked by the
+setter and again by every call; ``common_prefix_rows()`` is the most it can be) ``decode_attention`` forwards
+to ``ops/paged_cascade_attention.py``, which reads the shared pages once per KV head for the whole batch, on MFMAs,
+and only the rows behind them per sequence.  The default 0 keeps ``paged_decode_attention`` and its bits.
+
 Not supported (each raises ``ValueError``): an FP8 pool, block steps (``extend_attention``), appending into
 a page that is still shared (no copy-on-write), and the device-geometry form a captured graph needs.
 """
@@ -80,6 +85,7 @@ class PagedKVCache:
         self._ws: torch.Tensor | None = None
         self._scatter: tuple | None = None  # fill's index tensors, dropped when the table changes
         self._view: tuple | None = None  # seq_view's gathered rows, dropped when a table row or a length changes
+        self._cascade_rows = 0
 
     # ------------------------------------------------------------------ allocation (host)
     def _upload(self, b: int) -> None:
@@ -133,6 +139,41 @@ class PagedKVCache:
 
     def owned_rows(self, b: int) -> int:
         return len(self.table[b]) * PAGE
+
+    def common_prefix_rows(self) -> int:
+        """Rows of the largest whole-page prefix whose pool pages every sequence's table names (host tables
+        only): ``P`` after ``share_prefix(0, b, P)`` for all ``b``, 0 for sequences that share nothing."""
+        n = 0
+        for ids in zip(*self.table):
+            if any(p != ids[0] for p in ids):
+                break
+            n += 1
+        return n * PAGE
+
+    def check_shared_rows(self, rows: int, what: str = "PagedKVCache") -> None:
+        """Raise ``ValueError`` unless the first ``rows`` rows are whole pages that every sequence holds
+        (``rows <= min(lens)``) and shares (the host tables agree on their first ``rows / PAGE`` entries)."""
+        rows = int(rows)
+        if rows <= 0 or rows % PAGE:
+            raise ValueError(f"{what}: {rows} shared rows are not a positive number of whole pages of {PAGE}")
+        if rows > min(self.lens):
+            raise ValueError(f"{what}: {rows} shared rows exceed the shortest sequence ({min(self.lens)} rows)")
+        n = rows // PAGE
+        if any(t[:n] != self.table[0][:n] for t in self.table):
+            raise ValueError(f"{what}: the sequences' tables differ inside their first {n} pages; "
+                             f"common_prefix_rows() is {self.common_prefix_rows()}")
+
+    @property
+    def cascade_rows(self) -> int:
+        """Rows that ``decode_attention`` reads once for the whole batch (``ops/paged_cascade_attention.py``);
+        0, the default, keeps the per-sequence kernel."""
+        return self._cascade_rows
+
+    @cascade_rows.setter
+    def cascade_rows(self, rows: int) -> None:
+        if int(rows) != 0:
+            self.check_shared_rows(rows, "PagedKVCache.cascade_rows")
+        self._cascade_rows = int(rows)
 
     # ------------------------------------------------------------------ rows
     def k(self, layer: int) -> torch.Tensor:

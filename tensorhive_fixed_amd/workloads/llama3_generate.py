@@ -35,6 +35,9 @@ prompts are made so, prompts from ``--prompt-ids`` are checked.  The page-aligne
 once and its pages are shared by every sequence (``Llama.generate(shared_prefix=N)``,
 ``ops/paged_chunk_attention.py``); the JSON line then carries ``shared_prefix``, ``kv_pages`` (the pool) and
 ``prefix_pages`` (the shared part of it) beside ``prefill_ms``.
+``--cascade-decode`` (needs ``--shared-prefix``) makes every decode step's attention read those shared pages once
+for the whole batch (``Llama.generate(cascade=True)``, ``ops/paged_cascade_attention.py``); the JSON line then
+carries ``cascade: true``.
 ``--repeat-prompt N`` makes the synthetic prompts repeat an N-token pattern, which prompt lookup can use.
 
 The project has no tokenizer: prompts are token ids, from ``--prompt-ids FILE`` (a JSON list of id
@@ -153,6 +156,9 @@ def main(argv: list[str] | None = None) -> int:
     ap.add_argument("--shared-prefix", type=int, default=None, metavar="N",
                     help="the first N tokens of every prompt are the same: prefill their whole pages once and share "
                          "them (ops/paged_chunk_attention.py); needs --paged-kv")
+    ap.add_argument("--cascade-decode", action="store_true",
+                    help="decode steps read the shared prefix once per batch (ops/paged_cascade_attention.py, "
+                         "csrc/paged_cascade_attn.hip); needs --shared-prefix")
     ap.add_argument("--repeat-prompt", type=int, default=0, metavar="N",
                     help="synthetic prompts repeat an N-token pattern")
     args = ap.parse_args(argv)
@@ -171,6 +177,8 @@ def main(argv: list[str] | None = None) -> int:
             ap.error("--shared-prefix needs --paged-kv")
         if not args.prompt_ids:
             tokens[:, : args.shared_prefix] = tokens[:1, : args.shared_prefix]
+    if args.cascade_decode and args.shared_prefix is None:
+        ap.error("--cascade-decode needs --shared-prefix")
     sampler = torch.Generator(device=device)
     sampler.manual_seed(args.seed + 1)
 
@@ -214,7 +222,8 @@ def main(argv: list[str] | None = None) -> int:
                          top_k=args.top_k, generator=sampler, on_step=on_step, stream_gemm=args.stream_gemm,
                          graph=args.graph, fp8=args.fp8_weights, kv_fp8=args.fp8_kv, speculate=args.speculate,
                          draft_fn=draft_fn, spec_stats=spec_stats, prefill_chunk=args.prefill_chunk,
-                         paged_kv=args.paged_kv, mxfp4=args.mxfp4_weights, shared_prefix=args.shared_prefix)
+                         paged_kv=args.paged_kv, mxfp4=args.mxfp4_weights, shared_prefix=args.shared_prefix,
+                         cascade=args.cascade_decode)
     end = sync()
     spec = {}
     if args.speculate:
@@ -239,6 +248,8 @@ def main(argv: list[str] | None = None) -> int:
         paged = {"paged_kv": True, "kv_dense_mb": round(kv_bytes / 2 ** 20, 1), "kv_pages": n_pages}
         if args.shared_prefix is not None:
             paged.update(shared_prefix=args.shared_prefix, prefix_pages=pages_for(P))
+        if args.cascade_decode:
+            paged.update(cascade=True)
         kv_bytes = paged_cache_bytes(cfg, n_pages)
         print(f"[th-gen] paged KV pool {kv_bytes} bytes, the dense cache would take "
               f"{kv_cache_bytes(cfg, batch, max(lens) + args.max_new_tokens)} bytes", flush=True)
